@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: uniform_filter(size=5) on a 512^3 float32 volume.
 
-    python bench.py --gpus N --steps K --warmup W [--config H|E] [--scaling strong|weak]
+    python bench.py --gpus N --steps K --warmup W [--config H|E] [--scaling strong|weak] [--dump-outputs DIR]
 
 Default (--config H, the metric of BASELINE.json).  N = 1: one fused HIP launch per step on a device-resident volume
 (cupyimg_amd.scipy.ndimage.uniform_filter -> mi_separable3d_f32).
@@ -53,6 +53,42 @@ ALG_BYTES_PER_VOXEL = 8        # read 4 + write 4
 
 def synth(shape, seed=0):
     return np.random.default_rng(seed).standard_normal(shape, dtype=np.float32)
+
+
+# --dump-outputs: the whole 512^3 result is 512 MiB, so what is written is a fixed sample of it -- the first and last
+# z-plane (where the boundary mode acts) and the voxels at DUMP_SAMPLES seeded flat indices of the whole volume.  The
+# indices are global, so a slab-split run writes the same files as a single-GPU run of the same volume.
+DUMP_SEED = 20261015
+DUMP_SAMPLES = 1 << 22          # 16 MiB of float32; with two 2048^2 planes (config E) 48 MiB in all
+DUMP_CHUNK_BYTES = 256 << 20    # device-to-host copies of at most this many bytes at a time
+
+
+def output_sample(dev, z0, nz):
+    """This rank's part of the dump sample of an (nz, Y, X) result whose planes z0 .. z0 + len(dev) are `dev` (device
+    array): (sampled values in index order, {z: plane} of the first / last z-plane of the volume held here)."""
+    plane = dev.shape[1] * dev.shape[2]
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, nz * plane, DUMP_SAMPLES, dtype=np.int64))
+    z1 = z0 + dev.shape[0]
+    mine = idx[np.searchsorted(idx, z0 * plane):np.searchsorted(idx, z1 * plane)] - z0 * plane
+    vals = np.empty(mine.size, dev.dtype)
+    step = max(1, DUMP_CHUNK_BYTES // (plane * dev.dtype.itemsize))
+    for a in range(0, dev.shape[0], step):
+        b = min(a + step, dev.shape[0])
+        s0, s1 = np.searchsorted(mine, [a * plane, b * plane])
+        vals[s0:s1] = dev[a:b].get().reshape(-1)[mine[s0:s1] - a * plane]
+    faces = {z: dev[z - z0].get() for z in (0, nz - 1) if z0 <= z < z1}
+    return vals, faces
+
+
+def write_dump(directory, parts, name):
+    """Merges the ranks' `output_sample` parts (in rank order) and writes DIR/<name>_sample.npy (1-D) and
+    DIR/<name>_faces.npy (2, Y, X), in the result's dtype (float32)."""
+    os.makedirs(directory, exist_ok=True)
+    faces = {}
+    for _, f in parts:
+        faces.update(f)
+    np.save(os.path.join(directory, name + "_sample.npy"), np.concatenate([v for v, _ in parts]))
+    np.save(os.path.join(directory, name + "_faces.npy"), np.stack([faces[z] for z in sorted(faces)]))
 
 
 SETTLE_LAUNCHES = 220        # ~ 40 ms of the 2 x 512 MiB copy kernel before the comparators are timed
@@ -445,8 +481,15 @@ def main():
                     help="functional dry run of the N > 1 code path on ONE GPU: the rank is both neighbours of itself (closed chain, "
                          "`wrap` along z) over a one-rank RCCL communicator -- exchange, schedule tuning, seam parity all execute; "
                          "the number it prints is not a benchmark result")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed seeded sample of what the last step computed to "
+                         "DIR/uniform_filter_sample.npy and DIR/uniform_filter_faces.npy (float32), for comparing builds")
     ap.add_argument("--cpu-allcores-helper", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
     if args.cpu_allcores_helper:
         allcores_helper(args.cpu_allcores_helper)
         return
@@ -621,6 +664,16 @@ def main():
         settle_device(ca)
     elapsed, dev_ms = timed_region()
     kernel_name = last_kernel()
+    if args.dump_outputs:
+        # read before anything else runs: the configs block below reuses `out`
+        part = output_sample(out, 0, nz_total) if sf is None else output_sample(sf.local_out, plan.z0, nz_total)
+        parts = [part]
+        if dist is not None:
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object(part, parts, dst=0)
+        if rank == 0:
+            write_dump(args.dump_outputs, parts, "uniform_filter")
+        del part, parts
 
     # ------------------------------------------------------------ parity of the distributed / slab result (untimed)
     slab_ok = seam_err = None
