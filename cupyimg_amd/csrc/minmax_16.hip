@@ -867,6 +867,7 @@ extern "C" int mi_uniform2d_16(const mi_array *in, const mi_array *out, const in
     hipStream_t s = resolve_stream(stream);
     const uint16_t *ip = (const uint16_t *)in->data;
     uint16_t *op = (uint16_t *)out->data;
+    note_kernel("mi::box2d_16_kernel<%d,%d,%s> (uniform_filter in integer arithmetic: y and x windows)", wx, wy, is_signed ? "int16" : "uint16");
     switch (wx) {
     case 1: return launch_box16_wy<1>(wy, ip, op, p, is_signed, s);
     case 3: return launch_box16_wy<3>(wy, ip, op, p, is_signed, s);
@@ -902,6 +903,7 @@ extern "C" int mi_uniform_z_16(const mi_array *in, const mi_array *out, int size
     p.cval2 = ((unsigned)cval & 0xFFFFu) * 0x10001u;
     p.nxt = (int)((nx + 511) / 512);
     p.ry = (float)(1.0 / size_z); p.rx = 1.0f;
+    note_kernel("mi::box2d_16_kernel<1,%d,%s> (uniform_filter in integer arithmetic: z window)", size_z, is_signed ? "int16" : "uint16");
     return launch_box16_wy<1>(size_z, (const uint16_t *)in->data, (uint16_t *)out->data, p, is_signed, resolve_stream(stream));
 #undef UNSUP
 }

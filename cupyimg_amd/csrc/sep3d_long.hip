@@ -48,9 +48,9 @@ struct LongParams {
     // y / z weights, each one TWICE (an aligned SGPR pair is what v_pk_fma_f32 takes: no s_mov per odd tap)
     float wyv[2 * kStreamMaxTaps], wzv[2 * kStreamMaxTaps];
     float xpair[2][2 * (kStreamMaxTaps / 2 + 2)];   // see StreamParams::xpair
-    // constant mode (HAS_CONST kernels): plain x weights, cval, cval * (product of the three weight sums)
+    // constant mode (HAS_CONST kernels): plain x weights, cval, cval * sx and cval * sx * sy (sums of the x / y weights)
     float wxs[kStreamMaxTaps];
-    float cval, cval_sum;
+    float cval, cval_sx, cval_sxy;
     // sep3d_long3_kernel: plain weights padded with a zero (pairs starting at an even tap); wxo[2k] = wx[2k-1],
     // wxo[2k+1] = wx[2k] (pairs starting at an odd tap; wxo[0] = 0)
     float wyp[kStreamMaxTaps + 1], wzp[kStreamMaxTaps + 1], wxe[kStreamMaxTaps + 1], wxo[kStreamMaxTaps + 1];
@@ -117,6 +117,7 @@ sep3d_long_kernel(const float *__restrict__ in, float *__restrict__ out, const L
     constexpr unsigned HY0 = kLongRawBytes;
     int *ztab = reinterpret_cast<int *>(smem + kLongRawBytes + kLongHyBytes);
     float *cztab = reinterpret_cast<float *>(ztab + kLongMaxChunk + kStreamMaxTaps);     // HAS_CONST: z coverage per output plane
+    float *oztab = cztab + kLongMaxChunk;                                                   // HAS_CONST: z weight outside per output plane
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -151,31 +152,40 @@ sep3d_long_kernel(const float *__restrict__ in, float *__restrict__ out, const L
     // Constant mode: the DMA cannot substitute cval, but it zero-fills what lies outside (out-of-range lanes, rows and
     // planes), and  filter(x extended by cval) = filter(x extended by 0) + cval * (S - cz(z) cy(y) cx(x)),  S = product
     // of the three weight sums, c_a(i) = sum of the axis-a weights whose tap lands inside the volume (all of them on
-    // an axis that is not in constant mode).  cz per output plane goes to an LDS table, cy is one number per wave,
-    // cx four per lane: the correction is two packed FMAs per output float4.
-    [[maybe_unused]] float cyv = 0.f;
-    [[maybe_unused]] F4 cxv = f4_splat(0.f);
+    // an axis that is not in constant mode).  With o_a = s_a - c_a, the sum of the taps that land outside, the correction
+    // is evaluated as  cval * (oz sy sx + cz oy sx + cz cy ox):  every term is zero where its axis stays inside, so an
+    // output whose window does not leave the volume gets exactly nothing added -- the form  cval * S - cval * cz cy cx
+    // cancelled two terms of size |cval| in float32 and left an error of order 2^-24 |cval| on EVERY voxel (a fill of
+    // -1024 on CT data: 100x the rounding of the filter itself).  cz / oz per output plane go to an LDS table, cy / oy
+    // are one number per wave row, ox four per lane: the correction is still two packed FMAs per output float4.
+    [[maybe_unused]] float cyv = 0.f, oyv = 0.f;
+    [[maybe_unused]] F4 oxv = f4_splat(0.f);
     if constexpr (HAS_CONST) {
         for (int t = threadIdx.x; t < ze - zs; t += kLongTY * 64) {
-            float c = 0.f;
+            float c = 0.f, o = 0.f;
             for (int k = 0; k < W; k++) {
                 const int q = zs + t - p.oz + k;
-                c += (p.mz != MI_MODE_CONSTANT || (q >= 0 && q < nz)) ? p.wzv[2 * k] : 0.f;
+                const bool in = p.mz != MI_MODE_CONSTANT || (q >= 0 && q < nz);
+                c += in ? p.wzv[2 * k] : 0.f;
+                o += in ? 0.f : p.wzv[2 * k];
             }
             cztab[t] = c;
+            oztab[t] = o;
         }
-        float cx4[4] = {0.f, 0.f, 0.f, 0.f};
+        float ox4[4] = {0.f, 0.f, 0.f, 0.f};
         for (int k = 0; k < W; k++) {
             const int qy = y0 + wave - p.oy + k;
-            cyv += (p.my != MI_MODE_CONSTANT || (qy >= 0 && qy < ny)) ? p.wyv[2 * k] : 0.f;
+            const bool iny = p.my != MI_MODE_CONSTANT || (qy >= 0 && qy < ny);
+            cyv += iny ? p.wyv[2 * k] : 0.f;
+            oyv += iny ? 0.f : p.wyv[2 * k];
 #pragma unroll
             for (int c = 0; c < 4; c++) {
                 const int qx = x0 + 4 * lane + c - W / 2 + k;
-                cx4[c] += (p.mx != MI_MODE_CONSTANT || (qx >= 0 && qx < nx)) ? p.wxs[k] : 0.f;
+                ox4[c] += (p.mx != MI_MODE_CONSTANT || (qx >= 0 && qx < nx)) ? 0.f : p.wxs[k];
             }
         }
-        cxv.lo = (f32x2){cx4[0], cx4[1]};
-        cxv.hi = (f32x2){cx4[2], cx4[3]};
+        oxv.lo = (f32x2){ox4[0], ox4[1]};
+        oxv.hi = (f32x2){ox4[2], ox4[3]};
     }
     __syncthreads();
 
@@ -296,9 +306,11 @@ sep3d_long_kernel(const float *__restrict__ in, float *__restrict__ out, const L
                     const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void *)oa, 0, (int)plane_bytes, 0x00020000);
                     F4 o = acc[(J + 1) % W];
                     if constexpr (HAS_CONST) {
-                        const float g = -p.cval * cztab[i - (W - 1)] * cyv;
-                        o.lo = fma2(splat2(g), cxv.lo, o.lo + splat2(p.cval_sum));
-                        o.hi = fma2(splat2(g), cxv.hi, o.hi + splat2(p.cval_sum));
+                        const float czv = cztab[i - (W - 1)];
+                        const float g1 = p.cval * czv * cyv;
+                        const float g0 = oztab[i - (W - 1)] * p.cval_sxy + czv * (p.cval_sx * oyv);
+                        o.lo = fma2(splat2(g1), oxv.lo, o.lo + splat2(g0));
+                        o.hi = fma2(splat2(g1), oxv.hi, o.hi + splat2(g0));
                     }
                     if (!(p.dbg & 16)) __builtin_amdgcn_raw_buffer_store_b128(f4_to_u32(o), rout, ovoff, 0, 2);
                 }
@@ -334,6 +346,7 @@ sep3d_long2_kernel(const float *__restrict__ in, float *__restrict__ out, const 
     constexpr unsigned HY0 = kLongRawBytes;
     int *ztab = reinterpret_cast<int *>(smem + kLongRawBytes + kLongHyBytes);
     float *cztab = reinterpret_cast<float *>(ztab + kLongMaxChunk + kStreamMaxTaps);
+    float *oztab = cztab + kLongMaxChunk;
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -365,32 +378,37 @@ sep3d_long2_kernel(const float *__restrict__ in, float *__restrict__ out, const 
     const int nsteps = ze - zs + W - 1;
 
     for (int i = threadIdx.x; i < nsteps; i += NW * 64) ztab[i] = bmap<int>(zi0 + i, nz, p.mz);
-    [[maybe_unused]] float cyv[2] = {0.f, 0.f};
-    [[maybe_unused]] F4 cxv = f4_splat(0.f);
+    [[maybe_unused]] float cyv[2] = {0.f, 0.f}, oyv[2] = {0.f, 0.f};
+    [[maybe_unused]] F4 oxv = f4_splat(0.f);
     if constexpr (HAS_CONST) {
         for (int t = threadIdx.x; t < ze - zs; t += NW * 64) {
-            float c = 0.f;
+            float c = 0.f, o = 0.f;
             for (int k = 0; k < W; k++) {
                 const int q = zs + t - p.oz + k;
-                c += (p.mz != MI_MODE_CONSTANT || (q >= 0 && q < nz)) ? p.wzv[2 * k] : 0.f;
+                const bool in = p.mz != MI_MODE_CONSTANT || (q >= 0 && q < nz);
+                c += in ? p.wzv[2 * k] : 0.f;
+                o += in ? 0.f : p.wzv[2 * k];
             }
             cztab[t] = c;
+            oztab[t] = o;
         }
-        float cx4[4] = {0.f, 0.f, 0.f, 0.f};
+        float ox4[4] = {0.f, 0.f, 0.f, 0.f};
         for (int k = 0; k < W; k++) {
 #pragma unroll
             for (int r = 0; r < 2; r++) {
                 const int qy = y0 + 2 * wave + r - p.oy + k;
-                cyv[r] += (p.my != MI_MODE_CONSTANT || (qy >= 0 && qy < ny)) ? p.wyv[2 * k] : 0.f;
+                const bool iny = p.my != MI_MODE_CONSTANT || (qy >= 0 && qy < ny);
+                cyv[r] += iny ? p.wyv[2 * k] : 0.f;
+                oyv[r] += iny ? 0.f : p.wyv[2 * k];
             }
 #pragma unroll
             for (int c = 0; c < 4; c++) {
                 const int qx = x0 + 4 * lane + c - W / 2 + k;
-                cx4[c] += (p.mx != MI_MODE_CONSTANT || (qx >= 0 && qx < nx)) ? p.wxs[k] : 0.f;
+                ox4[c] += (p.mx != MI_MODE_CONSTANT || (qx >= 0 && qx < nx)) ? 0.f : p.wxs[k];
             }
         }
-        cxv.lo = (f32x2){cx4[0], cx4[1]};
-        cxv.hi = (f32x2){cx4[2], cx4[3]};
+        oxv.lo = (f32x2){ox4[0], ox4[1]};
+        oxv.hi = (f32x2){ox4[2], ox4[3]};
     }
     __syncthreads();
 
@@ -526,9 +544,11 @@ sep3d_long2_kernel(const float *__restrict__ in, float *__restrict__ out, const 
                     for (int r = 0; r < 2; r++) {
                         F4 o = acc[r][(J + 1) % W];
                         if constexpr (HAS_CONST) {
-                            const float g = -p.cval * cztab[i - (W - 1)] * cyv[r];
-                            o.lo = fma2(splat2(g), cxv.lo, o.lo + splat2(p.cval_sum));
-                            o.hi = fma2(splat2(g), cxv.hi, o.hi + splat2(p.cval_sum));
+                            const float czv = cztab[i - (W - 1)];
+                            const float g1 = p.cval * czv * cyv[r];
+                            const float g0 = oztab[i - (W - 1)] * p.cval_sxy + czv * (p.cval_sx * oyv[r]);
+                            o.lo = fma2(splat2(g1), oxv.lo, o.lo + splat2(g0));
+                            o.hi = fma2(splat2(g1), oxv.hi, o.hi + splat2(g0));
                         }
                         if (!(p.dbg & 16)) __builtin_amdgcn_raw_buffer_store_b128(f4_to_u32(o), rout, ovoff[r], 0, 2);
                     }
@@ -1229,7 +1249,7 @@ template <int W, bool SAME, bool HAS_CONST>
 static int launch_long(const float *in, float *out, LongParams &p, hipStream_t s)
 {
     const size_t lds = (size_t)kLongRawBytes + kLongHyBytes + (size_t)(kLongMaxChunk + kStreamMaxTaps) * sizeof(int) +
-                       (HAS_CONST ? (size_t)kLongMaxChunk * sizeof(float) : 0);
+                       (HAS_CONST ? (size_t)2 * kLongMaxChunk * sizeof(float) : 0);      // cztab, oztab
     const int total = p.nxt * p.nyt * p.nzc;
     if constexpr (HAS_CONST) {
         // r5: a zero fill value needs no correction at all -- zero fill is what the staging leaves for whatever lies beyond
@@ -1356,7 +1376,7 @@ int run_sep3d_long(const float *in, float *out, int nz, int ny, int nx, int w, i
     p.nxt = (nx + 255) / 256;
     p.tw = (((nx + p.nxt - 1) / p.nxt) + 3) & ~3;          // equal tiles (see separable3d.hip)
     p.nyt = (ny + kLongTY - 1) / kLongTY;
-    double sx = 0, sy = 0, sz = 0;
+    double sx = 0, sy = 0;
     for (int k = 0; k < w; k++) {
         p.wyv[2 * k] = p.wyv[2 * k + 1] = wy[k];
         p.wxs[k] = wx[k];
@@ -1367,12 +1387,12 @@ int run_sep3d_long(const float *in, float *out, int nz, int ny, int nx, int w, i
     for (int k = 0; k < wzn; k++) {
         p.wzv[2 * k] = p.wzv[2 * k + 1] = wz[k];
         p.wzp[k] = wz[k];
-        sz += wz[k];
     }
     p.dbg = g_long_dbg;
     p.nt = stream_nt_for((long long)nz * ny * nx * 8, p.nxt);
     p.cval = cval;
-    p.cval_sum = (float)((double)cval * sx * sy * sz);
+    p.cval_sx = (float)((double)cval * sx);
+    p.cval_sxy = (float)((double)cval * sx * sy);
     {
         const int rx = w / 2, nb = (rx + 3) / 4, base = 4 * nb - rx;
         for (int q = 0; q < 2; q++) {

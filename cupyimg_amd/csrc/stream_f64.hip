@@ -284,6 +284,7 @@ static int launch_stream_d(const double *in, double *out, StreamParamsD &p, hipS
     p.nchunks = (nA + p.chunk - 1) / p.chunk;
     const int waves = nlines * p.nchunks;
     p.swz = xcd_swizzle_for((size_t)p.nx * p.ny * p.nz * 8);
+    note_kernel("mi::stream_pass_f64_kernel<%d,%d,%d,%d> grid=%d", WX, WA, DEPTH, (int)OP, (waves + 3) / 4);
     hipLaunchKernelGGL((stream_pass_f64_kernel<WX, WA, DEPTH, OP>), dim3((waves + 3) / 4), dim3(256), 0, s, in, out, p);
     MI_HIP(hipGetLastError());
     return MI_OK;

@@ -216,7 +216,12 @@ int mi_uniform_filter1d(const mi_array *in, const mi_array *out, int axis, int s
  * (filters.py:602-665, :725-792; _filters_core.py:148-155).
  * weights[a] (host, wlen[a] doubles) may be NULL for an axis that is not
  * filtered.  is_box != 0: all given weights are 1/wlen (sum-then-scale path).
- * Returns MI_ERR_UNSUPPORTED when no fused kernel covers the request. */
+ * Returns MI_ERR_UNSUPPORTED when no fused kernel covers the request.
+ * Precision: weights, cval, products and partial sums are float32 whatever the
+ * caller's dtype_mode (the reference accumulates in float64 by default).  The
+ * tested bound, per output voxel: |out - exact| <= c * 2^-24 * B, where B is the
+ * same filter applied to |in| with |weights| and |cval|, and c = sum over the
+ * filtered axes of (wlen + 2) (tests/test_gpu_value_ranges.py). */
 int mi_separable3d_f32(const mi_array *in, const mi_array *out, const double *const weights[3],
                        const int wlen[3], const int origin[3], const int mode[3], double cval,
                        int is_box, mi_stream stream);
@@ -245,6 +250,10 @@ int mi_separable3d_f32_supports(const mi_array *in, const mi_array *out, const d
 int mi_correlate_nd(const mi_array *in, const mi_array *out, const double *weights,
                     const int64_t *wshape, const int *origins, int mode, double cval,
                     int acc_f32, mi_stream stream);
+/* Precision of the dense float32 kernels: acc_f32 == 0 accumulates in float64 and
+ * rounds once (bit-identical to SciPy); acc_f32 != 0 (stencil3s_kernel in float
+ * mode) accumulates in float32, tested to |out - exact| <= (n + 2) * 2^-24 * B with
+ * n the nonzero weights and B the correlate of |in| with |weights| and |cval|. */
 /* The dense 3 x 3 x 3 / 5 x 5 x 5 (with acc_f32: 7 x 7 x 7) window without zero weights on a float32 volume through stencil3s_kernel only
  * -- rows of ANY length, x origin 0 -- or MI_ERR_UNSUPPORTED with nothing queued (mi_correlate_nd never refuses: it ends at the
  * generic gather kernel).  For callers that would otherwise extend ragged rows for the tiled kernel (filters.py:65-210). */

@@ -1,8 +1,14 @@
 """Randomised differential test of the HIP path against scipy.ndimage (run on the GPU box).
-usage: python scripts/fuzz_vs_scipy.py [seconds] [seed] [max cases]   -- prints mismatches with their parameters.
-env FUZZ_ONLY=op1,op2 restricts the op families, FUZZ_TRACE=1 prints every case before it runs."""
+usage: python scripts/fuzz_vs_scipy.py [--ranges] [seconds] [seed] [max cases]   -- prints mismatches with their parameters.
+env FUZZ_ONLY=op1,op2 restricts the op families, FUZZ_TRACE=1 prints every case before it runs.
+--ranges: a separate draw on the value ranges of real scans (MR 0 .. 4095, CT Hounsfield units with padding, 1e4 + noise,
+full-range 16-bit integers; tests/helpers/value_ranges.py): float results are judged per voxel by |got - ref64| <= c u B,
+integer results bit for bit.  Without it the draw is the seeded one tests/test_gpu_fuzz.py depends on."""
 import os, sys, time, traceback
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+RANGES = "--ranges" in sys.argv
+if RANGES:
+    sys.argv.remove("--ranges")
 import numpy as np
 import scipy.ndimage as sndi
 import cupyimg_amd as ca
@@ -199,6 +205,95 @@ def case():
 
 def ndi_gt0(a):
     return a          # binary ops treat any non-zero as foreground
+
+
+def ranges_case():
+    """(name, params, x, device call, SciPy call, bound or None for bit-exact) of the --ranges draw."""
+    from helpers import value_ranges as vr
+    nd = int(rng.choice([2, 3, 3]))
+    shape = (tuple(int(v) for v in rng.integers(8, 48, size=2)) if nd == 3 else (int(rng.integers(8, 200)),)) + \
+        (int(rng.choice([rng.integers(8, 130), 4 * rng.integers(2, 40), 256])),)
+    gen = str(rng.choice(["mr_u12", "ct_hu", "offset_1e4", "extremes", "mr_u12_u16", "ct_hu_i16"]))
+    seed = int(rng.integers(1 << 30))
+    if gen in ("mr_u12", "ct_hu", "offset_1e4"):
+        x = vr.offset_1e4(shape, seed) if gen == "offset_1e4" else getattr(vr, gen)(shape, seed, dtype=np.float32)
+        mode = str(rng.choice(MODES + ["grid-wrap", "grid-constant"]))
+        cval = float(rng.choice([0.0, -1024.0, -1000.3, 4095.0]))
+        kind = str(rng.choice(["uniform", "gaussian", "sobel", "prewitt", "correlate"]))
+        if kind == "uniform":
+            size = [int(rng.choice([1, 3, 5, 7, 9, 13])) for _ in range(nd)]
+            w = vr.box_spec(nd, size)
+            f = lambda m, a: m.uniform_filter(a, size, mode=mode, cval=cval)
+            params = (shape, gen, kind, size, mode, cval)
+        elif kind == "gaussian":
+            sig = [float(rng.choice([0.0, 0.7, 1.0, 1.5, 2.0, 3.0])) for _ in range(nd)]
+            od = [int(rng.choice([0, 0, 1, 2])) for _ in range(nd)]
+            if not any(s_ > 0 for s_ in sig):
+                sig[-1] = 1.0
+            w = vr.gaussian_spec(nd, sig, od)
+            f = lambda m, a: m.gaussian_filter(a, sig, od, mode=mode, cval=cval)
+            params = (shape, gen, kind, sig, od, mode, cval)
+        elif kind in ("sobel", "prewitt"):
+            ax = int(rng.integers(nd))
+            w = vr.deriv_spec(nd, ax, [1, 2, 1] if kind == "sobel" else [1, 1, 1])
+            f = lambda m, a: getattr(m, kind)(a, ax, mode=mode, cval=cval)
+            params = (shape, gen, kind, ax, mode, cval)
+            return kind, params, x, f, (vr.abs_separable(w, mode, cval, vr.deriv_order(nd, ax)), vr.sep_c(w))
+        else:
+            wt = rng.standard_normal((3,) * nd)
+            f = lambda m, a: m.correlate(a, wt, mode=mode, cval=cval, dtype_mode="float") if m is ndi else \
+                m.correlate(a.astype(np.float64), wt, mode=mode, cval=cval)
+            params = (shape, gen, "correlate(float mode)", mode, cval)
+            return kind, params, x, f, (vr.abs_dense(wt, mode, cval), vr.dense_c(wt))
+        return kind, params, x, f, (vr.abs_separable(w, mode, cval), vr.sep_c(w))
+    dt = np.uint16 if gen in ("mr_u12_u16",) or (gen == "extremes" and rng.random() < 0.5) else np.int16
+    x = vr.mr_u12(shape, seed) if gen == "mr_u12_u16" else vr.ct_hu(shape, seed) if gen == "ct_hu_i16" else vr.int_extremes(shape, dt, seed)
+    info = np.iinfo(x.dtype)
+    mode = str(rng.choice(MODES))
+    cval = float(rng.choice([0.0, float(info.min), float(info.max)]))
+    kind = str(rng.choice(["uniform", "minimum", "maximum", "median3", "grey_erosion"]))
+    size = [int(rng.choice([1, 3, 5, 7, 9])) for _ in range(nd)]
+    if kind == "uniform":
+        f = lambda m, a: m.uniform_filter(a, size, mode=mode, cval=cval)
+    elif kind in ("minimum", "maximum"):
+        f = lambda m, a: getattr(m, kind + "_filter")(a, size, mode=mode, cval=cval)
+    elif kind == "median3":
+        f = lambda m, a: m.median_filter(a, 3, mode=mode, cval=cval)
+    else:
+        f = lambda m, a: m.grey_erosion(a, size=size, mode=mode, cval=cval)
+    return kind, (shape, gen, str(x.dtype), kind, size, mode, cval), x, f, None
+
+
+def run_ranges():
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from helpers import value_ranges as vr
+    t_end = time.time() + budget
+    n = fails = 0
+    worst = {}
+    while time.time() < t_end and n < max_cases:
+        name, params, x, f, bound = ranges_case()
+        if os.environ.get("FUZZ_TRACE"):
+            print("TRACE", name, params, flush=True)
+        got = f(ndi, ca.asarray(x)).get()
+        n += 1
+        if bound is None:
+            ok = np.array_equal(got, f(sndi, x))
+            r = 0.0 if ok else float("inf")
+        else:
+            x64 = x.astype(np.float64)
+            r, at = vr.ratio_of(got, np.asarray(f(sndi, x64), np.float64), bound[0](np.abs(x64)), bound[1])
+            ok = r <= 1.0
+        key = name + (" exact" if bound is None else " bound")
+        worst[key] = max(worst.get(key, 0.0), r)
+        if not ok:
+            fails += 1
+            print("MISMATCH", name, params, "ratio", r, "kernel", ca.last_kernel(), flush=True)
+    print("ranges: cases %d, failures %d, worst ratio per op %s" % (n, fails, {k: round(v, 4) for k, v in sorted(worst.items())}))
+    return fails
+
+
+if RANGES:
+    sys.exit(1 if run_ranges() else 0)
 
 t_end = time.time() + budget
 n = fails = skipped = 0
