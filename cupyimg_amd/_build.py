@@ -76,6 +76,8 @@ SOURCES = [
     ("cubic_fast.hip", ["-ffp-contract=off"]),
     ("halo.hip", []),
     ("metrics.hip", ["-ffp-contract=off"]),
+    ("label.hip", []),
+    ("measure.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function",
           "-I" + os.path.join(os.path.dirname(HERE), "include")]

@@ -99,6 +99,8 @@ SIGNATURES = {
     "mi_ssim_products": [_arr, _arr, _arr, _arr, _arr, _vp],
     "mi_ssim_combine_mean": [_arr, _arr, _arr, _arr, _arr, _arr, _i, _d, _d, _d, _dp, _vp],
     "mi_ssim_combine": [_arr] * 9 + [_d, _d, _d, _vp],
+    "mi_label": [_arr, _arr, _u8p, _i, ctypes.c_int64, _i64p, _vp],
+    "mi_labeled_reduce": [_i, _arr, _arr, _arr, ctypes.c_int64, ctypes.c_int64, _i, _dp, _i, _arr, _arr, _vp],
     "mi_correlate1d": [_arr, _arr, _i, _dp, _i, _i, _i, _d, _i, _vp],
     "mi_uniform_filter1d": [_arr, _arr, _i, _i, _i, _i, _d, _vp],
     "mi_separable3d_f32": [_arr, _arr, ctypes.POINTER(_dp), _ip, _ip, _ip, _d, _i, _vp],

@@ -1,0 +1,321 @@
+"""scipy.ndimage measurements on device arrays: label and the labelled reductions.
+
+Same signatures and results as cupyimg/scipy/ndimage/measurements.py (label :29, sum :316, mean :388, variance :428,
+standard_deviation :470, minimum :689, maximum :739, minimum_position :842, maximum_position :895, extrema :950,
+center_of_mass :1003, histogram :1066).  All voxel work runs in csrc/label.hip and csrc/measure.hip; this module
+massages arguments.  `median` and `labeled_comprehension` are not provided (a per-label median needs a segmented
+select; labeled_comprehension takes a Python callable).
+
+Return kinds follow the reference: values are device arrays (0-d for a scalar or absent `index`), positions and centres
+of mass are host tuples (a list of tuples for a sequence `index`).
+"""
+import ctypes
+
+import numpy as np
+
+from ... import core
+from . import _support as S
+
+__all__ = [
+    "label", "sum", "sum_labels", "mean", "variance", "standard_deviation", "minimum", "maximum",
+    "minimum_position", "maximum_position", "extrema", "center_of_mass", "histogram",
+]
+
+_MAX_VOXELS = 2 ** 31
+
+
+def _generate_binary_structure(rank, connectivity):
+    if connectivity < 1:
+        connectivity = 1
+    if rank < 1:
+        return np.array(True, dtype=bool)
+    return np.abs(np.indices([3] * rank) - 1).sum(axis=0) <= connectivity
+
+
+def _label(input, structure, output, greyscale_mode=False, background=0):
+    """Label `input` (device, any non-complex dtype) into the int32 device array `output`; returns num_features."""
+    input = core.ascontiguousarray(input)
+    if input.size >= _MAX_VOXELS:
+        raise ValueError("label: arrays of 2**31 voxels or more are not supported (int32 labels); got {} voxels"
+                         .format(input.size))
+    st = np.ascontiguousarray(structure, dtype=np.uint8)
+    num = ctypes.c_int64()
+    a, o = input._desc(), output._desc()
+    S.check(S.lib().mi_label(ctypes.byref(a), ctypes.byref(o), st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                             int(bool(greyscale_mode)), int(background), ctypes.byref(num), None))
+    return int(num.value)
+
+
+def label(input, structure=None, output=None, *, greyscale_mode=False):
+    """Label features of an array (scipy.ndimage.label; measurements.py:29-93).
+
+    Returns ``(labels, num_features)``, or ``num_features`` alone when `output` is an array.  Synchronises the device
+    once (the feature count)."""
+    input = S.as_device(input)            # complex input: TypeError
+    if input.dtype == np.float16:
+        input = input.astype(np.float32)  # exact; only "non-zero" and equality matter
+    if structure is None:
+        structure = _generate_binary_structure(input.ndim, 1)
+    structure = np.asarray(S.as_host(structure), dtype=bool)
+    if structure.ndim != input.ndim:
+        raise RuntimeError("structure and input must have equal rank")
+    for i in structure.shape:
+        if i != 3:
+            raise ValueError("structure dimensions must be equal to 3")
+    if isinstance(output, core.ndarray):
+        if output.shape != input.shape:
+            raise ValueError("output shape not correct")
+        output._touch()
+        caller_provided_output = True
+    else:
+        caller_provided_output = False
+        output = core.empty(input.shape, np.int32 if output is None else np.dtype(output))
+    if input.size == 0:
+        maxlabel = 0
+    elif input.ndim == 0:
+        maxlabel = 0 if input.reshape(1).get()[0] == 0 else 1
+        output.fill(maxlabel)
+    else:
+        y = output if output.dtype == np.int32 and output._is_c_contiguous() else core.empty(input.shape, np.int32)
+        maxlabel = _label(input, structure, y, greyscale_mode=greyscale_mode)
+        if y is not output:
+            _check_bit_depth(output.dtype, maxlabel)
+            output[...] = y            # the conversion pass (mi_copy)
+    if output.dtype != np.int32:
+        _check_bit_depth(output.dtype, maxlabel)
+    if caller_provided_output:
+        return maxlabel
+    return output, maxlabel
+
+
+def _check_bit_depth(dtype, maxlabel):
+    dtype = np.dtype(dtype)
+    if dtype.kind in "iu" and maxlabel > np.iinfo(dtype).max or dtype.kind == "b" and maxlabel > 1:
+        raise RuntimeError("insufficient bit-depth in requested output type")
+
+
+# ------------------------------------------------------------------ labelled reductions
+_OPS = {"sum": 0, "mean": 1, "variance": 2, "std": 3, "extrema": 4, "com": 5, "hist": 6}
+_LUT_SLACK = 1 << 16
+
+
+def _prepare(input, labels, index):
+    """(input, labels, index_dev, imin, imax, sorted_flag, K, scalar, restore) for mi_labeled_reduce.  `restore` maps
+    results over the unique sorted index back to the caller's order (None when the lookup-table path is used)."""
+    input = S.as_device(input)
+    if input.dtype == np.float16:
+        input = input.astype(np.float32)
+    input = core.ascontiguousarray(input)
+    if labels is None:
+        if index is not None:
+            raise ValueError("index given without labels")
+        return input, None, None, 0, 0, 0, 1, True, None
+    labels = S.as_device(labels)
+    if labels.dtype.kind not in "biu":
+        raise TypeError("labels must be of integer or bool dtype")
+    if labels.shape != input.shape:
+        labels = _broadcast(labels, input.shape)
+    ldt = np.int64 if labels.dtype.itemsize > 4 or labels.dtype == np.uint32 else np.int32
+    labels = core.ascontiguousarray(labels, dtype=ldt)
+    if index is None:
+        return input, labels, None, 0, 0, 0, 1, True, None
+    scalar = False
+    if isinstance(index, core.ndarray):
+        idx_dev = core.ascontiguousarray(index.reshape(-1) if index.ndim != 1 else index, dtype=np.int64)
+        if idx_dev.size == 0:
+            return input, labels, idx_dev, 0, 0, 0, 0, False, None
+        lo, hi = S.min_max(idx_dev)
+        imin, imax = int(lo), int(hi)
+        idx_host = None
+    else:
+        arr = np.asarray(index)
+        scalar = arr.ndim == 0
+        idx_host = np.ascontiguousarray(arr.reshape(-1), dtype=np.int64)
+        if idx_host.size == 0:
+            return input, labels, None, 0, 0, 0, 0, False, None
+        imin, imax = int(idx_host.min()), int(idx_host.max())
+        idx_dev = None
+    K = idx_dev.size if idx_dev is not None else idx_host.size
+    if imax - imin < 4 * K + _LUT_SLACK:
+        if idx_dev is None:
+            idx_dev = core.asarray(idx_host)
+        return input, labels, idx_dev, imin, imax, 0, K, scalar, None
+    # wide range: binary search over the sorted unique values; results are put back in the caller's order
+    if idx_host is None:
+        idx_host = idx_dev.get()
+    uniq, inv = np.unique(idx_host, return_inverse=True)
+    return input, labels, core.asarray(uniq), int(uniq[0]), int(uniq[-1]), 1, uniq.size, scalar, inv
+
+
+def _broadcast(labels, shape):
+    try:
+        bshape = np.broadcast_shapes(labels.shape, shape)
+    except ValueError:
+        raise ValueError("labels and input must have broadcastable shapes")
+    if bshape != tuple(shape):
+        raise ValueError("labels and input must have broadcastable shapes")
+    nd = len(shape)
+    lshape = (1,) * (nd - labels.ndim) + labels.shape
+    lstrides = (0,) * (nd - labels.ndim) + labels.strides
+    strides = tuple(0 if ls == 1 and s != 1 else st for ls, s, st in zip(lshape, shape, lstrides))
+    return labels._view(tuple(shape), strides, labels.ptr)
+
+
+def _reduce(op, input, labels, index, out_dtype=np.float64, positions=False, hist=None):
+    inp, lab, idx, imin, imax, srt, K, scalar, restore = _prepare(input, labels, index)
+    if op == _OPS["extrema"]:
+        out_dtype, width = inp.dtype, 2
+    elif op == _OPS["com"]:
+        width = inp.ndim
+    elif op == _OPS["hist"]:
+        out_dtype, width = np.int64, hist[1] + 1
+    else:
+        width = 1
+    out = core.empty((max(K, 1), width), out_dtype)
+    pos = core.empty((max(K, 1), 2), np.int64) if positions else None
+    if K == 0:
+        return out[0:0], (pos[0:0] if pos is not None else None), scalar, restore, inp.shape
+    edges_arr = None
+    bins = 0
+    if hist is not None:
+        edges_arr, bins = hist
+    a = inp._desc()
+    la = lab._desc() if lab is not None else None
+    ia = idx._desc() if idx is not None else None
+    oa = out._desc()
+    pa = pos._desc() if pos is not None else None
+    S.check(S.lib().mi_labeled_reduce(
+        op, ctypes.byref(a), ctypes.byref(la) if la is not None else None, ctypes.byref(ia) if ia is not None else None,
+        imin, imax, srt, edges_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if edges_arr is not None else None,
+        bins, ctypes.byref(oa), ctypes.byref(pa) if pa is not None else None, None))
+    return out, pos, scalar, restore, inp.shape
+
+
+def _values(out, scalar, restore, index):
+    """Device result of shape (K, 1) -> 0-d (scalar / no index) or 1-D in the caller's order."""
+    flat = out.reshape(out.shape[0])
+    if restore is not None:
+        flat = core.asarray(flat.get()[restore])
+    if index is None or scalar:
+        return flat.reshape(()) if flat.size == 1 else flat
+    shape = np.shape(index) if not isinstance(index, core.ndarray) else index.shape
+    return flat.reshape(shape) if len(shape) != 1 else flat
+
+
+def _stat(op, input, labels, index):
+    out, _, scalar, restore, _ = _reduce(_OPS[op], input, labels, index)
+    return _values(out, scalar, restore, index)
+
+
+def sum_labels(input, labels=None, index=None):
+    """Sum of the values per label (scipy.ndimage.sum_labels; measurements.py:316-385), float64."""
+    return _stat("sum", input, labels, index)
+
+
+sum = sum_labels
+
+
+def mean(input, labels=None, index=None):
+    """Mean per label (measurements.py:388-425); NaN for an index value no voxel carries."""
+    return _stat("mean", input, labels, index)
+
+
+def variance(input, labels=None, index=None):
+    """Variance per label, two passes (measurements.py:428-467)."""
+    return _stat("variance", input, labels, index)
+
+
+def standard_deviation(input, labels=None, index=None):
+    """Standard deviation per label (measurements.py:470-507)."""
+    return _stat("std", input, labels, index)
+
+
+def _extrema(input, labels, index, positions):
+    out, pos, scalar, restore, shape = _reduce(_OPS["extrema"], input, labels, index, positions=positions)
+    return out, pos, scalar, restore, shape
+
+
+def _column(out, col, scalar, restore, index):
+    K = out.shape[0]
+    v = out[:, col] if K else out.reshape(0)
+    return _values(core.ascontiguousarray(v).reshape(K, 1) if K else out.reshape(0, 1), scalar, restore, index)
+
+
+def _positions(pos, col, scalar, restore, index, shape):
+    p = pos.get()[:, col] if pos.shape[0] else np.zeros(0, np.int64)
+    if restore is not None:
+        p = p[restore]
+    coords = [tuple(int(c) for c in np.unravel_index(int(v), shape)) for v in p] if len(shape) else [() for _ in p]
+    if index is None or scalar:
+        return coords[0]
+    return coords
+
+
+def minimum(input, labels=None, index=None):
+    """Minimum per label (measurements.py:689-736); 0 for an index value no voxel carries.  NaN is skipped unless a
+    region holds nothing else.  Input dtype."""
+    out, _, scalar, restore, _ = _extrema(input, labels, index, False)
+    return _column(out, 0, scalar, restore, index)
+
+
+def maximum(input, labels=None, index=None):
+    """Maximum per label (measurements.py:739-786); NaN where a region holds a NaN."""
+    out, _, scalar, restore, _ = _extrema(input, labels, index, False)
+    return _column(out, 1, scalar, restore, index)
+
+
+def minimum_position(input, labels=None, index=None):
+    """Position of the first minimum per label, as host tuples (measurements.py:842-892)."""
+    _, pos, scalar, restore, shape = _extrema(input, labels, index, True)
+    return _positions(pos, 0, scalar, restore, index, shape)
+
+
+def maximum_position(input, labels=None, index=None):
+    """Position of the first maximum per label (of the last NaN where the maximum is NaN), host tuples
+    (measurements.py:895-947)."""
+    _, pos, scalar, restore, shape = _extrema(input, labels, index, True)
+    return _positions(pos, 1, scalar, restore, index, shape)
+
+
+def extrema(input, labels=None, index=None):
+    """(minimums, maximums, min_positions, max_positions) per label (measurements.py:950-1000), one pass of each kind."""
+    out, pos, scalar, restore, shape = _extrema(input, labels, index, True)
+    return (_column(out, 0, scalar, restore, index), _column(out, 1, scalar, restore, index),
+            _positions(pos, 0, scalar, restore, index, shape), _positions(pos, 1, scalar, restore, index, shape))
+
+
+def center_of_mass(input, labels=None, index=None):
+    """Centre of mass per label as host tuples of floats (measurements.py:1003-1063); value and value x coordinate of
+    every axis are summed in one pass."""
+    out, _, scalar, restore, shape = _reduce(_OPS["com"], input, labels, index)
+    res = out.get() if out.shape[0] else np.zeros((0, len(shape)))
+    if restore is not None:
+        res = res[restore]
+    rows = [tuple(float(c) for c in r) for r in res]
+    if index is None or scalar:
+        return rows[0]
+    return rows
+
+
+def histogram(input, min, max, bins, labels=None, index=None):
+    """Histogram per label (measurements.py:1066-1110; scipy: numpy.histogram(values, linspace(min, max, bins + 1))):
+    bin k counts edges[k] <= v < edges[k + 1] against those float64 edges, the last bin closed.  Counts are int64
+    device arrays; with a sequence `index` a list of one array per index value, None for a value no voxel carries."""
+    inp = S.as_device(input)
+    bins = int(bins)
+    edges = np.ascontiguousarray(np.linspace(min, max, bins + 1), dtype=np.float64)
+    out, _, scalar, restore, _ = _reduce(_OPS["hist"], inp, labels, index, hist=(edges, bins))
+    K = out.shape[0]
+    # column `bins` counts the region's voxels outside the edges: a row summing to 0 is a region no voxel carries
+    present = out.get().sum(axis=1) > 0 if K else np.zeros(0, bool)
+    if restore is not None:
+        host = out.get()[restore]
+        present = present[restore]
+        rows = [core.asarray(r[:bins]) for r in host]
+    else:
+        rows = [out[k, 0:bins] for k in range(K)]
+    if labels is not None and index is not None:
+        rows = [r if p else None for r, p in zip(rows, present)]      # SciPy's labeled_comprehension default
+    if index is None or scalar:
+        return rows[0]
+    return rows

@@ -194,6 +194,34 @@ int mi_ssim_combine_mean(const mi_array *ux, const mi_array *uy, const mi_array 
                          mi_stream stream);
 
 /* ------------------------------------------------------------------ */
+/* K8: measurements (label and labelled reductions)                     */
+/* ------------------------------------------------------------------ */
+/* Connected components of a contiguous array of rank 1..8 and fewer than 2**31 voxels, numbered as
+ * scipy.ndimage.label numbers them (cupyimg/scipy/ndimage/measurements.py:29-199): raster order of each feature's
+ * first voxel.  A voxel is foreground when it differs from `background` (0 for scipy; skimage.measure.label's
+ * `background`, skimage/measure/_label.py:108-114; a background the input dtype cannot hold equals no voxel); `structure` is 3**ndim bytes, assumed centrosymmetric.
+ * greyscale != 0 connects only neighbours of equal value (measurements.py:145-199, skimage semantics).  `out` is int32,
+ * contiguous, of the input's shape (it holds the union-find parents until the last pass); *num_features is written on
+ * the host (the call synchronises the stream). */
+int mi_label(const mi_array *in, const mi_array *out, const uint8_t *structure, int greyscale, int64_t background,
+             int64_t *num_features, mi_stream stream);
+/* Labelled reductions (measurements.py:316-1464): op 0 sum, 1 mean, 2 variance, 3 standard deviation (float64 out,
+ * one value per index entry), 4 extrema (out: input dtype (K, 2) = minimum, maximum; out_pos, optional: int64 (K, 2)
+ * linear indices of the first minimum and first maximum in C order, of the LAST NaN where the maximum is NaN),
+ * 5 center of mass (float64 (K, ndim)), 6 histogram (int64 (K, bins + 1): bin k counts edges[k] <= v < edges[k + 1],
+ * the last bin closed, as numpy.histogram against scipy's float64 linspace(min, max, bins + 1) `edges`; the extra last
+ * column counts the region's voxels outside [edges[0], edges[bins]] and NaNs, so a region with no voxel sums to 0).
+ * `labels` (int32 / int64, or NULL: one region of every voxel) has the input's shape; `index` (int64, K values in
+ * [imin, imax], or NULL: the voxels with labels > 0 form one region) names the regions: a lookup table over
+ * [imin, imax] unless sorted_index != 0 (index sorted and unique: binary search).  An index value no voxel carries
+ * gives sum 0, NaN for the means and centres, 0 for extrema and positions.  Sums are in float64 with atomic adds:
+ * integer inputs are exact below 2**53, float results vary in their last bits with the atomics' arrival order (not
+ * bit-reproducible from run to run).  float16 inputs are converted to float32 by the caller. */
+int mi_labeled_reduce(int op, const mi_array *in, const mi_array *labels, const mi_array *index, int64_t imin,
+                      int64_t imax, int sorted_index, const double *edges, int bins,
+                      const mi_array *out, const mi_array *out_pos, mi_stream stream);
+
+/* ------------------------------------------------------------------ */
 /* K1: correlate family                                                 */
 /* ------------------------------------------------------------------ */
 /* One separable pass: out[.., o, ..] = sum_k w[k] * ext(in)[.., o - (wlen/2 + origin) + k, ..]
