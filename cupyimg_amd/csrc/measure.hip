@@ -5,7 +5,8 @@
 // Index -> slot.  `index` (K int64 values on the device) names the regions.  When its range imax - imin is small (the usual
 // arange(1, n + 1) after label) a lookup table lut[v - imin] = smallest k with index[k] == v is built on the device (one
 // atomicMin scatter); otherwise the caller passes index sorted and unique and each voxel binary-searches it.  Without an
-// index every voxel with label > 0 (labels given) or every voxel (no labels) falls in slot 0.
+// index every voxel with label > 0 (labels given; label != 0 for uint64 labels the caller passed as int64) or every voxel
+// (no labels) falls in slot 0.
 //
 // Atomic budget (reduce on chip first, one atomic per destination and workgroup).  A wave covers 64 consecutive voxels; runs of equal slots inside
 // the wave are first reduced by shuffles (segmented doubling), and only each run's head lane issues an atomic.  With few
@@ -25,7 +26,7 @@ constexpr int kLdsSlots = 1024;
 constexpr int kLdsCom = 2048;             // LDS accumulators of center_of_mass: slots x axes
 
 enum MeasOp { M_SUMS = 0, M_SSD = 1, M_EXT = 2, M_POS = 3, M_COM = 4, M_HIST = 5 };
-enum SlotMode { S_ALL = 0, S_POSITIVE = 1, S_LUT = 2, S_SEARCH = 3 };
+enum SlotMode { S_ALL = 0, S_POSITIVE = 1, S_LUT = 2, S_SEARCH = 3, S_NONZERO = 4 };
 
 struct SlotMap {
     int mode;
@@ -53,14 +54,15 @@ struct MeasAcc {
 
 template <typename T> struct is_float_t { static constexpr bool value = std::is_floating_point<T>::value; };
 
-// order-preserving 64-bit key; NaN above everything (maximum: any NaN wins; minimum: NaN only if nothing else)
+// order-preserving 64-bit key; NaN above everything (maximum: any NaN wins; minimum: NaN only if nothing else).  -0.0 and
+// +0.0 share +0.0's key, as they compare equal in SciPy: the first of them in C order is the extreme's position.
 template <typename T>
 __device__ __forceinline__ unsigned long long to_key(T v)
 {
     if constexpr (std::is_floating_point<T>::value) {
         const double d = (double)v;
         if (d != d) return ~0ull;
-        const unsigned long long b = (unsigned long long)__double_as_longlong(d);
+        const unsigned long long b = d == 0.0 ? 0ull : (unsigned long long)__double_as_longlong(d);
         return (b >> 63) ? ~b : (b | (1ull << 63));
     } else if constexpr (std::is_same<T, uint64_t>::value) {
         return v;
@@ -93,6 +95,7 @@ __device__ __forceinline__ int slot_of(const L *__restrict__ lab, int64_t i, con
     if (m.mode == S_ALL) return 0;
     const int64_t v = (int64_t)lab[i];
     if (m.mode == S_POSITIVE) return v > 0 ? 0 : -1;
+    if (m.mode == S_NONZERO) return v != 0 ? 0 : -1;
     if (v < m.imin || v > m.imax) return -1;
     if (m.mode == S_LUT) {
         const int s = m.lut[v - m.imin];
@@ -288,10 +291,10 @@ __global__ void __launch_bounds__(256) meas_finalize_kernel(int op, MeasAcc acc,
         const bool present = acc.kmin[s] <= acc.kmax[s];
         outv[2 * k] = present ? from_key<T>(acc.kmin[s]) : T(0);
         outv[2 * k + 1] = present ? from_key<T>(acc.kmax[s]) : T(0);
-        if (outp) {
-            outp[2 * k] = present ? (int64_t)acc.pmin[s] : 0;
+        if (outp) {             // -1: no voxel carries the value; 0 where it does when no position pass ran (pmin null)
             const bool last = is_float_t<T>::value && acc.kmax[s] == ~0ull;
-            outp[2 * k + 1] = present ? (last ? (int64_t)acc.pmax_last[s] : (int64_t)acc.pmax_first[s]) : 0;
+            outp[2 * k] = !present ? -1 : acc.pmin ? (int64_t)acc.pmin[s] : 0;
+            outp[2 * k + 1] = !present ? -1 : !acc.pmin ? 0 : last ? (int64_t)acc.pmax_last[s] : (int64_t)acc.pmax_first[s];
         }
         break;
     }
@@ -310,7 +313,7 @@ static int meas_grid(int64_t n)
 }
 
 static const char *const kOpName[] = {"M_SUMS", "M_SSD", "M_EXT", "M_POS", "M_COM", "M_HIST"};
-static const char *const kSlotName[] = {"all", "positive", "lut", "search"};
+static const char *const kSlotName[] = {"all", "positive", "lut", "search", "nonzero"};
 
 // appends "<kernel and route>" to `what` (the name mi_debug_last_kernel reports for the call)
 template <typename T, typename L, int OP>
@@ -371,7 +374,12 @@ int mi_labeled_reduce(int op, const mi_array *in, const mi_array *labels, const 
 {
     int rc;
     if ((rc = check_array(in, "input")) || (rc = check_array(out, "output"))) return rc;
-    MI_REQUIRE(op >= 0 && op <= 6, MI_ERR_INVALID_ARG, "unknown labelled reduction");
+    const int flags = op & ~0xff;
+    op &= 0xff;
+    MI_REQUIRE(op >= 0 && op <= 6 && (flags & ~(MI_REDUCE_NONZERO | MI_REDUCE_PRESENCE)) == 0, MI_ERR_INVALID_ARG,
+               "unknown labelled reduction");
+    MI_REQUIRE(!(flags & MI_REDUCE_PRESENCE) || (op == 4 && out_pos), MI_ERR_INVALID_ARG,
+               "MI_REDUCE_PRESENCE: extrema with out_pos");
     MI_REQUIRE(is_contiguous(in) && is_contiguous(out), MI_ERR_NOT_CONTIGUOUS, "mi_labeled_reduce needs C-contiguous arrays");
     MI_REQUIRE(in->dtype != MI_F16, MI_ERR_INVALID_ARG, "float16 input: convert to float32 first");
     if (labels) {
@@ -406,7 +414,7 @@ int mi_labeled_reduce(int op, const mi_array *in, const mi_array *labels, const 
     m.nslot = K;
     m.imin = imin;
     m.imax = imax;
-    m.mode = !labels ? S_ALL : !index ? S_POSITIVE : sorted_index ? S_SEARCH : S_LUT;
+    m.mode = !labels ? S_ALL : !index ? ((flags & MI_REDUCE_NONZERO) ? S_NONZERO : S_POSITIVE) : sorted_index ? S_SEARCH : S_LUT;
     const int64_t lutn = m.mode == S_LUT ? imax - imin + 1 : 0;
     const int nd = in->ndim;
     // workspace: lut | rep | cnt | sum | ssd | mean | kmin | kmax | pmin | pmaxf | pmaxl | com | hist | edges
@@ -440,7 +448,7 @@ int mi_labeled_reduce(int op, const mi_array *in, const mi_array *labels, const 
     for (int d = 0; d < nd; d++) acc.shape[d] = in->shape[d];
     acc.bins = bins;
     acc.edges = dedges;
-    if (!out_pos) { acc.pmin = nullptr; }
+    if (!out_pos || (flags & MI_REDUCE_PRESENCE)) { acc.pmin = nullptr; }      // no M_POS pass
 
     hipError_t e = hipSuccess;
     if (e == hipSuccess) e = hipMemsetAsync(acc0, 0, zero_end - acc0, s);
@@ -458,7 +466,7 @@ int mi_labeled_reduce(int op, const mi_array *in, const mi_array *labels, const 
     }
     if (m.mode == S_SEARCH) m.sorted = idx;
     if (m.mode == S_LUT) hipLaunchKernelGGL(meas_rep_kernel, dim3((K + 255) / 256), dim3(256), 0, s, idx, K, m, rep);
-    else e = hipMemsetAsync(rep, 0, S * 4, s);          // S_ALL / S_POSITIVE: one slot; S_SEARCH: identity, set below
+    else e = hipMemsetAsync(rep, 0, S * 4, s);          // S_ALL / S_POSITIVE / S_NONZERO: one slot; S_SEARCH: identity, set below
     if (m.mode == S_SEARCH) hipLaunchKernelGGL(meas_rep_kernel, dim3((K + 255) / 256), dim3(256), 0, s, idx, K, m, rep);
 
     if (n > 0) {

@@ -96,12 +96,16 @@ def _check_bit_depth(dtype, maxlabel):
 
 # ------------------------------------------------------------------ labelled reductions
 _OPS = {"sum": 0, "mean": 1, "variance": 2, "std": 3, "extrema": 4, "com": 5, "hist": 6}
+_NONZERO = 0x100        # MI_REDUCE_NONZERO: with no index the region is labels != 0
+_PRESENCE = 0x200       # MI_REDUCE_PRESENCE: extrema report only whether a voxel carries each value (no position pass)
 _LUT_SLACK = 1 << 16
 
 
 def _prepare(input, labels, index):
-    """(input, labels, index_dev, imin, imax, sorted_flag, K, scalar, restore) for mi_labeled_reduce.  `restore` maps
-    results over the unique sorted index back to the caller's order (None when the lookup-table path is used)."""
+    """(input, labels, index_dev, imin, imax, sorted_flag, K, scalar, restore, flags, absent) for mi_labeled_reduce.
+    `restore` maps results over the unique sorted index back to the caller's order (None when the lookup-table path
+    is used).  `flags`: _NONZERO for uint64 labels with no index.  `absent` (or None): the caller's index entries that
+    name no label whatever the labels hold; they are left out of the reduction and filled in by _reduce."""
     input = S.as_device(input)
     if input.dtype == np.float16:
         input = input.astype(np.float32)
@@ -109,42 +113,81 @@ def _prepare(input, labels, index):
     if labels is None:
         if index is not None:
             raise ValueError("index given without labels")
-        return input, None, None, 0, 0, 0, 1, True, None
+        return input, None, None, 0, 0, 0, 1, True, None, 0, None
     labels = S.as_device(labels)
     if labels.dtype.kind not in "biu":
         raise TypeError("labels must be of integer or bool dtype")
     if labels.shape != input.shape:
         labels = _broadcast(labels, input.shape)
-    ldt = np.int64 if labels.dtype.itemsize > 4 or labels.dtype == np.uint32 else np.int32
-    labels = core.ascontiguousarray(labels, dtype=ldt)
+    u64 = labels.dtype == np.uint64
     if index is None:
-        return input, labels, None, 0, 0, 0, 1, True, None
+        # SciPy keeps labels > 0: for uint64 labels that is labels != 0, also for those that wrap negative as int64
+        return input, _as_int_labels(labels), None, 0, 0, 0, 1, True, None, _NONZERO if u64 else 0, None
     scalar = False
+    absent = None
     if isinstance(index, core.ndarray):
         idx_dev = core.ascontiguousarray(index.reshape(-1) if index.ndim != 1 else index, dtype=np.int64)
         if idx_dev.size == 0:
-            return input, labels, idx_dev, 0, 0, 0, 0, False, None
-        lo, hi = S.min_max(idx_dev)
-        imin, imax = int(lo), int(hi)
-        idx_host = None
+            return input, _as_int_labels(labels), idx_dev, 0, 0, 0, 0, False, None, 0, None
+        lo, hi = S.min_max(idx_dev)         # doubles: exact below 2**53 only
+        if max(abs(lo), abs(hi)) >= 2.0 ** 53 or (u64 and index.dtype.kind == "i" and lo < 0):
+            idx_host, idx_dev = idx_dev.get(), None
+            if u64 and index.dtype.kind == "i" and (idx_host < 0).any():
+                absent = idx_host < 0
+        else:
+            imin, imax = int(lo), int(hi)
+            idx_host = None
     else:
         arr = np.asarray(index)
         scalar = arr.ndim == 0
-        idx_host = np.ascontiguousarray(arr.reshape(-1), dtype=np.int64)
-        if idx_host.size == 0:
-            return input, labels, None, 0, 0, 0, 0, False, None
-        imin, imax = int(idx_host.min()), int(idx_host.max())
+        if arr.size == 0:
+            return input, _as_int_labels(labels), None, 0, 0, 0, 0, False, None, 0, None
+        idx_host, unmatched = _host_index(index, arr, u64)
+        if unmatched.any():
+            absent = unmatched
         idx_dev = None
+    labels = _as_int_labels(labels)
+    if absent is not None:
+        idx_host = idx_host[~absent]
+        if idx_host.size == 0:
+            return input, labels, None, 0, 0, 0, 0, scalar, None, 0, absent
+    if idx_host is not None:
+        imin, imax = int(idx_host.min()), int(idx_host.max())
     K = idx_dev.size if idx_dev is not None else idx_host.size
     if imax - imin < 4 * K + _LUT_SLACK:
         if idx_dev is None:
             idx_dev = core.asarray(idx_host)
-        return input, labels, idx_dev, imin, imax, 0, K, scalar, None
+        return input, labels, idx_dev, imin, imax, 0, K, scalar, None, 0, absent
     # wide range: binary search over the sorted unique values; results are put back in the caller's order
     if idx_host is None:
         idx_host = idx_dev.get()
     uniq, inv = np.unique(idx_host, return_inverse=True)
-    return input, labels, core.asarray(uniq), int(uniq[0]), int(uniq[-1]), 1, uniq.size, scalar, inv
+    return input, labels, core.asarray(uniq), int(uniq[0]), int(uniq[-1]), 1, uniq.size, scalar, inv, 0, absent
+
+
+def _as_int_labels(labels):
+    """int32 / int64 labels for the device (uint64 values of 2**63 and up wrap negative, equality is kept)"""
+    ldt = np.int64 if labels.dtype.itemsize > 4 or labels.dtype == np.uint32 else np.int32
+    return core.ascontiguousarray(labels, dtype=ldt)
+
+
+def _host_index(index, arr, u64):
+    """(int64 index values, entries that name no label).  Labels and index meet as int64, uint64 values of 2**63 and
+    up wrapped negative: a negative value then names no uint64 label, and a value of 2**63 or more no other label.
+    A list that mixes such large Python integers with small ones (NumPy makes it float64) is converted exactly."""
+    flat = arr.reshape(-1)
+    if arr.dtype.kind in "fO" and all(isinstance(v, (int, np.integer)) for v in np.asarray(index, dtype=object).flat):
+        vals = [int(v) for v in np.asarray(index, dtype=object).flat]
+        bad = np.array([v < 0 if u64 else v >= 1 << 63 for v in vals]) | \
+            np.array([not -(1 << 63) <= v < 1 << 64 for v in vals])
+        wrapped = np.array([v % (1 << 64) if -(1 << 63) <= v < 1 << 64 else 0 for v in vals], np.uint64)
+        return wrapped.view(np.int64).copy(), bad
+    idx = np.ascontiguousarray(flat, dtype=np.int64)
+    if arr.dtype.kind == "i" and u64:
+        return idx, flat < 0
+    if arr.dtype.kind == "u" and not u64:
+        return idx, flat >= np.uint64(1 << 63)
+    return idx, np.zeros(idx.size, bool)
 
 
 def _broadcast(labels, shape):
@@ -161,8 +204,8 @@ def _broadcast(labels, shape):
     return labels._view(tuple(shape), strides, labels.ptr)
 
 
-def _reduce(op, input, labels, index, out_dtype=np.float64, positions=False, hist=None):
-    inp, lab, idx, imin, imax, srt, K, scalar, restore = _prepare(input, labels, index)
+def _reduce(op, input, labels, index, out_dtype=np.float64, positions=False, hist=None, presence=False):
+    inp, lab, idx, imin, imax, srt, K, scalar, restore, flags, absent = _prepare(input, labels, index)
     if op == _OPS["extrema"]:
         out_dtype, width = inp.dtype, 2
     elif op == _OPS["com"]:
@@ -172,23 +215,45 @@ def _reduce(op, input, labels, index, out_dtype=np.float64, positions=False, his
     else:
         width = 1
     out = core.empty((max(K, 1), width), out_dtype)
-    pos = core.empty((max(K, 1), 2), np.int64) if positions else None
+    pos = core.empty((max(K, 1), 2), np.int64) if positions or presence else None
+    if presence and not positions:
+        flags |= _PRESENCE
     if K == 0:
-        return out[0:0], (pos[0:0] if pos is not None else None), scalar, restore, inp.shape
-    edges_arr = None
-    bins = 0
-    if hist is not None:
-        edges_arr, bins = hist
-    a = inp._desc()
-    la = lab._desc() if lab is not None else None
-    ia = idx._desc() if idx is not None else None
-    oa = out._desc()
-    pa = pos._desc() if pos is not None else None
-    S.check(S.lib().mi_labeled_reduce(
-        op, ctypes.byref(a), ctypes.byref(la) if la is not None else None, ctypes.byref(ia) if ia is not None else None,
-        imin, imax, srt, edges_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if edges_arr is not None else None,
-        bins, ctypes.byref(oa), ctypes.byref(pa) if pa is not None else None, None))
+        out, pos = out[0:0], (pos[0:0] if pos is not None else None)
+    else:
+        edges_arr = None
+        bins = 0
+        if hist is not None:
+            edges_arr, bins = hist
+        a = inp._desc()
+        la = lab._desc() if lab is not None else None
+        ia = idx._desc() if idx is not None else None
+        oa = out._desc()
+        pa = pos._desc() if pos is not None else None
+        S.check(S.lib().mi_labeled_reduce(
+            op | flags, ctypes.byref(a), ctypes.byref(la) if la is not None else None,
+            ctypes.byref(ia) if ia is not None else None, imin, imax, srt,
+            edges_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if edges_arr is not None else None,
+            bins, ctypes.byref(oa), ctypes.byref(pa) if pa is not None else None, None))
+    if absent is not None:
+        out, pos = _fill_absent(op, out, pos, restore, absent)
+        restore = None
     return out, pos, scalar, restore, inp.shape
+
+
+def _fill_absent(op, out, pos, restore, absent):
+    """results in the caller's index order with the rows of `absent` entries as for a value no voxel carries"""
+    fill = np.nan if op in (_OPS["mean"], _OPS["variance"], _OPS["std"], _OPS["com"]) else 0
+
+    def expand(a, value):
+        h = a.get() if a.shape[0] else np.zeros(a.shape, a.dtype)
+        if restore is not None:
+            h = h[restore]
+        full = np.empty((absent.size,) + h.shape[1:], h.dtype)
+        full[~absent] = h
+        full[absent] = value
+        return core.asarray(full)
+    return expand(out, fill), (expand(pos, -1) if pos is not None else None)
 
 
 def _values(out, scalar, restore, index):
@@ -231,7 +296,25 @@ def standard_deviation(input, labels=None, index=None):
 
 
 def _extrema(input, labels, index, positions):
-    out, pos, scalar, restore, shape = _reduce(_OPS["extrema"], input, labels, index, positions=positions)
+    input = S.as_device(input)
+    scalar_form = index is None or labels is None or np.ndim(index) == 0 and not isinstance(index, core.ndarray)
+    # a scalar form needs to know whether the region is empty: the positions when they are asked for anyway, else the
+    # presence flags of the extrema pass (no position pass, whose atomics grow with the ties of the extreme)
+    out, pos, scalar, restore, shape = _reduce(_OPS["extrema"], input, labels, index, positions=positions,
+                                               presence=scalar_form)
+    if scalar and out.shape[0] == 1:
+        # no index or a scalar one: SciPy reduces the region's values with vals.min() / vals.max(), which raise on an
+        # empty region and give NaN for the minimum when the region holds a NaN (its maximum is then NaN); with a
+        # sequence index NaN is skipped unless the region holds nothing else, as the kernel does
+        if int(pos.get()[0, 0]) < 0:
+            raise ValueError("zero-size array to reduction operation: no voxel carries the index value")
+        if input.dtype.kind == "f":
+            host = out.get()
+            if np.isnan(host[0, 1]) and not np.isnan(host[0, 0]):
+                host[0, 0] = np.nan
+                out = core.asarray(host)
+    if input.dtype == np.float16:
+        out = out.astype(np.float16)        # reduced in float32: exact, and SciPy answers in the input dtype
     return out, pos, scalar, restore, shape
 
 
@@ -242,7 +325,7 @@ def _column(out, col, scalar, restore, index):
 
 
 def _positions(pos, col, scalar, restore, index, shape):
-    p = pos.get()[:, col] if pos.shape[0] else np.zeros(0, np.int64)
+    p = np.maximum(pos.get()[:, col], 0) if pos.shape[0] else np.zeros(0, np.int64)      # absent (-1): (0, ..)
     if restore is not None:
         p = p[restore]
     coords = [tuple(int(c) for c in np.unravel_index(int(v), shape)) for v in p] if len(shape) else [() for _ in p]
@@ -252,8 +335,9 @@ def _positions(pos, col, scalar, restore, index, shape):
 
 
 def minimum(input, labels=None, index=None):
-    """Minimum per label (measurements.py:689-736); 0 for an index value no voxel carries.  NaN is skipped unless a
-    region holds nothing else.  Input dtype."""
+    """Minimum per label (measurements.py:689-736); 0 for an index value no voxel carries.  With a sequence index NaN
+    is skipped unless a region holds nothing else; with no index or a scalar one a NaN in the region is the minimum,
+    as in SciPy.  Input dtype."""
     out, _, scalar, restore, _ = _extrema(input, labels, index, False)
     return _column(out, 0, scalar, restore, index)
 
@@ -278,7 +362,9 @@ def maximum_position(input, labels=None, index=None):
 
 
 def extrema(input, labels=None, index=None):
-    """(minimums, maximums, min_positions, max_positions) per label (measurements.py:950-1000), one pass of each kind."""
+    """(minimums, maximums, min_positions, max_positions) per label (measurements.py:950-1000), one pass of each kind.
+    With no index or a scalar one, a region no voxel carries raises ValueError, as SciPy's vals.min() does (also for
+    minimum, maximum and the position functions)."""
     out, pos, scalar, restore, shape = _extrema(input, labels, index, True)
     return (_column(out, 0, scalar, restore, index), _column(out, 1, scalar, restore, index),
             _positions(pos, 0, scalar, restore, index, shape), _positions(pos, 1, scalar, restore, index, shape))
@@ -300,14 +386,35 @@ def center_of_mass(input, labels=None, index=None):
 def histogram(input, min, max, bins, labels=None, index=None):
     """Histogram per label (measurements.py:1066-1110; scipy: numpy.histogram(values, linspace(min, max, bins + 1))):
     bin k counts edges[k] <= v < edges[k + 1] against those float64 edges, the last bin closed.  Counts are int64
-    device arrays; with a sequence `index` a list of one array per index value, None for a value no voxel carries."""
+    device arrays; with a sequence `index` a 1-D object ndarray (as SciPy's labeled_comprehension) of one array per
+    index value, None for a value no voxel carries.  Raises ValueError, as SciPy does, when the edges decrease and some
+    region holds a voxel, for an empty sequence `index`, and for index values that do not survive a round trip through
+    the labels' dtype."""
     inp = S.as_device(input)
     bins = int(bins)
     edges = np.ascontiguousarray(np.linspace(min, max, bins + 1), dtype=np.float64)
+    labelled = labels is not None and index is not None
+    if labelled and (index.size if isinstance(index, core.ndarray) else np.size(index)) == 0:
+        raise ValueError("histogram: empty index")          # SciPy: a reduction over no regions
+    if labelled:
+        # scipy's labeled_comprehension: the index values must survive a round trip through the labels' dtype
+        ih = np.atleast_1d(index.get() if isinstance(index, core.ndarray) else index)
+        ldt = np.dtype(labels.dtype)
+        with np.errstate(all="ignore"):
+            lossy = bool(np.any(ih.astype(ldt).astype(ih.dtype) != ih))
+        if lossy:
+            raise ValueError("Cannot convert index values from <{}> to <{}> (labels' type) without loss of precision"
+                             .format(ih.dtype, ldt))
+        if ldt == np.uint64 and ih.dtype.kind == "i":
+            # SciPy compares labels with index.astype(labels.dtype): here -1 names the label 2**64 - 1
+            index = ih.astype(np.uint64) if np.ndim(index) else ih.astype(np.uint64)[0]
     out, _, scalar, restore, _ = _reduce(_OPS["hist"], inp, labels, index, hist=(edges, bins))
     K = out.shape[0]
     # column `bins` counts the region's voxels outside the edges: a row summing to 0 is a region no voxel carries
     present = out.get().sum(axis=1) > 0 if K else np.zeros(0, bool)
+    if np.any(edges[:-1] > edges[1:]) and (not labelled or present.any()):
+        # numpy.histogram's check, which SciPy reaches only for a region some voxel carries
+        raise ValueError("`bins` must increase monotonically, when an array")
     if restore is not None:
         host = out.get()[restore]
         present = present[restore]
@@ -318,4 +425,7 @@ def histogram(input, min, max, bins, labels=None, index=None):
         rows = [r if p else None for r, p in zip(rows, present)]      # SciPy's labeled_comprehension default
     if index is None or scalar:
         return rows[0]
-    return rows
+    res = np.empty(len(rows), dtype=object)          # as SciPy: an object array of count arrays (None: absent)
+    for k, r in enumerate(rows):
+        res[k] = r
+    return res

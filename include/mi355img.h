@@ -213,10 +213,15 @@ int mi_label(const mi_array *in, const mi_array *out, const uint8_t *structure, 
  * column counts the region's voxels outside [edges[0], edges[bins]] and NaNs, so a region with no voxel sums to 0).
  * `labels` (int32 / int64, or NULL: one region of every voxel) has the input's shape; `index` (int64, K values in
  * [imin, imax], or NULL: the voxels with labels > 0 form one region) names the regions: a lookup table over
- * [imin, imax] unless sorted_index != 0 (index sorted and unique: binary search).  An index value no voxel carries
- * gives sum 0, NaN for the means and centres, 0 for extrema and positions.  Sums are in float64 with atomic adds:
+ * [imin, imax] unless sorted_index != 0 (index sorted and unique: binary search).  Extrema and their positions treat
+ * -0.0 and +0.0 as equal.  An index value no voxel carries gives sum 0, NaN for the means and centres, 0 for extrema
+ * and -1 for positions.  Flags or'ed into `op`: MI_REDUCE_NONZERO (no index: the voxels with labels != 0 form the
+ * region, for uint64 labels passed as int64), MI_REDUCE_PRESENCE (op 4 with out_pos: out_pos gets 0 where a voxel
+ * carries the index value and -1 where none does, without the position pass).  Sums are in float64 with atomic adds:
  * integer inputs are exact below 2**53, float results vary in their last bits with the atomics' arrival order (not
  * bit-reproducible from run to run).  float16 inputs are converted to float32 by the caller. */
+#define MI_REDUCE_NONZERO 0x100
+#define MI_REDUCE_PRESENCE 0x200
 int mi_labeled_reduce(int op, const mi_array *in, const mi_array *labels, const mi_array *index, int64_t imin,
                       int64_t imax, int sorted_index, const double *edges, int bins,
                       const mi_array *out, const mi_array *out_pos, mi_stream stream);

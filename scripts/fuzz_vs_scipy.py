@@ -1,14 +1,26 @@
 """Randomised differential test of the HIP path against scipy.ndimage (run on the GPU box).
-usage: python scripts/fuzz_vs_scipy.py [--ranges] [seconds] [seed] [max cases]   -- prints mismatches with their parameters.
+usage: python scripts/fuzz_vs_scipy.py [--ranges | --measure] [seconds] [seed] [max cases]   -- prints mismatches with
+their parameters.
 env FUZZ_ONLY=op1,op2 restricts the op families, FUZZ_TRACE=1 prints every case before it runs.
 --ranges: a separate draw on the value ranges of real scans (MR 0 .. 4095, CT Hounsfield units with padding, 1e4 + noise,
 full-range 16-bit integers; tests/helpers/value_ranges.py): float results are judged per voxel by |got - ref64| <= c u B,
-integer results bit for bit.  Without it the draw is the seeded one tests/test_gpu_fuzz.py depends on."""
+integer results bit for bit.  Without it the draw is the seeded one tests/test_gpu_fuzz.py depends on.
+--measure: a separate draw of ndimage.label (ranks 1-4, shapes either side of the 8x16x32 / 1x64x64 tiles, every
+connectivity and random centrosymmetric structures, bool / integer / float inputs with NaN and -0.0, int32 / int64 /
+uint32 outputs; bit-exact against SciPy, a share of them also against the generic route) and of every labelled
+reduction (tests/helpers/measure_ref.py: the value ranges above with +-0, +-inf and NaN, every label dtype, index
+None / scalar / list / host / device array with duplicates, absent, 0 and negative values, slot counts around the LDS
+limits and index ranges either side of the lookup-table threshold).  Reductions are judged against a host float64
+reference with the bounds derived in measure_ref's docstring, exact where the result is an integer, an extreme, a
+position or a sum of integers; result type, shape, dtype and exceptions against SciPy."""
 import os, sys, time, traceback
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 RANGES = "--ranges" in sys.argv
 if RANGES:
     sys.argv.remove("--ranges")
+MEASURE = "--measure" in sys.argv
+if MEASURE:
+    sys.argv.remove("--measure")
 import numpy as np
 import scipy.ndimage as sndi
 import cupyimg_amd as ca
@@ -292,8 +304,100 @@ def run_ranges():
     return fails
 
 
+def label_case():
+    """(params, x, structure, output dtype) of the --measure draw's label cases"""
+    nd = int(rng.choice([1, 2, 2, 3, 3, 4]))
+    near = lambda: int(rng.choice([1, 2, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, rng.integers(2, 40)]))
+    if nd == 1:
+        shape = (int(rng.choice([1, 63, 64, 65, rng.integers(2, 5000)])),)
+    elif nd == 2:
+        shape = (near(), int(rng.choice([63, 64, 65, 127, 128, 129, near()])))
+    elif nd == 3:
+        shape = (int(rng.choice([1, 7, 8, 9, 15, 16, 17, rng.integers(2, 24)])), near(), int(rng.choice([31, 32, 33, 64, near()])))
+    else:
+        shape = tuple(int(rng.integers(1, 10)) for _ in range(4))
+    density = float(rng.choice([0.0, 1.0, rng.uniform(0.3, 0.7), rng.uniform(0.3, 0.7)]))
+    fg = rng.random(shape) < density
+    dtype = str(rng.choice(["bool", "uint8", "int16", "int32", "float32", "float64"]))
+    x = (fg * rng.integers(1, 4, shape)).astype(dtype)
+    if x.dtype.kind == "f":
+        x[fg & (rng.random(shape) < 0.1)] = np.nan               # NaN is foreground
+        x[~fg & (rng.random(shape) < 0.5)] = -0.0                # -0.0 is background
+    if rng.random() < 0.3:
+        st = rng.random((3,) * nd) > 0.5
+        st = st | st[(slice(None, None, -1),) * nd]
+        st[(1,) * nd] = True
+        sname = "random"
+    else:
+        conn = int(rng.integers(1, nd + 1))
+        st = sndi.generate_binary_structure(nd, conn)
+        sname = "conn%d" % conn
+    out = rng.choice([None, np.int64, np.uint32])
+    return (shape, dtype, round(density, 2), sname, None if out is None else np.dtype(out).name), x, st, out
+
+
+def run_measure():
+    import warnings
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from helpers import measure_ref as mr
+    from cupyimg_amd import _lib
+    lib = _lib.load()
+    warnings.simplefilter("ignore")
+    t_end = time.time() + budget
+    n = fails = 0
+    worst, counts = {}, {}
+    while time.time() < t_end and n < max_cases:
+        n += 1
+        if rng.random() < 0.3:
+            params, x, st, out = label_case()
+            if os.environ.get("FUZZ_TRACE"):
+                print("TRACE label", params, flush=True)
+            ref, rn = sndi.label(x, st, output=out)
+            got, gn = ndi.label(ca.asarray(x), st, output=out)
+            ok = gn == rn and got.dtype == ref.dtype and np.array_equal(got.get(), ref)
+            if ok and out is None and rng.random() < 0.35:      # the same labels from the generic route
+                lib.mi_debug_set_label_generic(1)
+                try:
+                    gen, _ = ndi.label(ca.asarray(x), st, output=out)
+                    ok = np.array_equal(gen.get(), got.get()) and ("label_connect_kernel" in ca.last_kernel() or x.size == 0 or x.ndim == 0)
+                finally:
+                    lib.mi_debug_set_label_generic(0)
+            counts["label"] = counts.get("label", 0) + 1
+            if not ok:
+                fails += 1
+                print("MISMATCH label", params, "num", gn, rn, "kernel", ca.last_kernel(), flush=True)
+            continue
+        case = mr.draw_reduction(rng)
+        desc = (case["func"], case["x"].shape, str(case["x"].dtype), case["gen"],
+                None if case["labels"] is None else str(case["labels"].dtype), case["index_kind"],
+                None if case["index"] is None else np.size(case["index"]), case["kw"])
+        if os.environ.get("FUZZ_TRACE"):
+            print("TRACE", desc, flush=True)
+        want = want_exc = got = got_exc = None
+        try:
+            want = mr.call(sndi, case)
+        except Exception as e:
+            want_exc = e
+        try:
+            got = mr.call(ndi, case, ca.asarray)
+        except Exception as e:
+            got_exc = e
+        ok, r, why = mr.judge(case, got, want, want_exc, got_exc)
+        counts[case["func"]] = counts.get(case["func"], 0) + 1
+        if r != float("inf"):
+            worst[case["func"]] = max(worst.get(case["func"], 0.0), r)
+        if not ok:
+            fails += 1
+            print("MISMATCH", desc, why, "kernel", ca.last_kernel(), flush=True)
+    print("measure: cases %d, failures %d, per op %s" % (n, fails, counts))
+    print("measure: worst bound ratio per op %s" % {k: round(v, 4) for k, v in sorted(worst.items())})
+    return fails
+
+
 if RANGES:
     sys.exit(1 if run_ranges() else 0)
+if MEASURE:
+    sys.exit(1 if run_measure() else 0)
 
 t_end = time.time() + budget
 n = fails = skipped = 0
