@@ -78,6 +78,7 @@ SOURCES = [
     ("metrics.hip", ["-ffp-contract=off"]),
     ("label.hip", []),
     ("measure.hip", ["-ffp-contract=off"]),
+    ("reconstruct.hip", []),
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function",
           "-I" + os.path.join(os.path.dirname(HERE), "include")]

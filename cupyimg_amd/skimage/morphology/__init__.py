@@ -1,22 +1,23 @@
 """skimage.morphology subset: grey and binary erosion / dilation / opening / closing,
-the top-hats and the structuring-element generators.
+the top-hats, grey-level reconstruction and the structuring-element generators.
 
 Behaviour follows cupyimg/skimage/morphology/grey.py:91-520 (+ `_shift_selem`
 :21-56, `_invert_selem` :59-89, `pad_for_eccentric_selems` :91-137), binary.py:11-135,
 selem.py and misc.py:24-47 (`default_selem`: cross-shaped connectivity-1 element of
-the image's rank)."""
+the image's rank); `reconstruction`: greyreconstruct.py:18-238."""
+import ctypes
 import functools
 
 import numpy as np
 
-from ... import core, _pad
+from ... import core, _lib, _pad
 from ...scipy import ndimage as ndi
 
 from ...scipy.ndimage import _support as S
 
 __all__ = ["erosion", "dilation", "opening", "closing", "white_tophat", "black_tophat", "binary_erosion",
            "binary_dilation", "binary_opening", "binary_closing", "square", "rectangle", "diamond", "disk", "cube",
-           "octahedron", "ball", "octagon", "star"]
+           "octahedron", "ball", "octagon", "star", "reconstruction"]
 
 
 def _default_selem(ndim):
@@ -192,6 +193,102 @@ def binary_closing(image, selem=None, out=None):
     """Binary dilation then erosion (binary.py:111-138)."""
     dilated = binary_dilation(image, selem)
     return binary_erosion(dilated, selem, out=out)
+
+
+# ---------------------------------------------------------------- grey-level reconstruction (greyreconstruct.py)
+_REC_MAX_GROUP = 4          # launches queued between two reads of the flags, at most
+_rec_launches = 0
+
+
+def last_reconstruction_launches():
+    """Launches of mi_grey_reconstruction_step the last `reconstruction` call of this process queued (the ones after the
+    image became stable included): a diagnostic for benchmarks and tests."""
+    return _rec_launches
+
+
+def reconstruction(seed, mask, method="dilation", selem=None, offset=None):
+    """Morphological reconstruction of `seed` under `mask` by dilation or erosion (greyreconstruct.py:18-238).
+
+    With S the offsets of the true cells of `selem` from its centre `offset` (centre removed), reconstruction by dilation
+    is the least image R >= seed that is stable under R[q] <- min(mask[q], max(R[q], max over d in S of R[q - d])); by
+    erosion min and max are swapped.  The reference runs its inner loop on the host; here every launch of
+    mi_grey_reconstruction_step moves the image towards that fixed point on the device (csrc/reconstruct.hip) and launches
+    repeat, ping-pong between two buffers, until a device flag stays 0.  The operator is monotone and only compares and
+    copies values, so the result is the reference's, bit for bit.  Result dtype: promote_types(seed.dtype, mask.dtype) as
+    in the reference (upstream skimage returns float64); always a new array."""
+    global _rec_launches
+    seed = _as_device(seed)
+    mask = _as_device(mask)
+    if tuple(seed.shape) != tuple(mask.shape):
+        raise ValueError("seed and mask must have the same shape")
+    if method not in ("dilation", "erosion"):
+        raise ValueError("Reconstruction method can be one of 'erosion' or 'dilation'. Got '%s'." % method)
+    if seed.ndim < 1 or seed.ndim > _lib.MI_MAX_NDIM:
+        raise ValueError("reconstruction takes arrays of rank 1 to {}".format(_lib.MI_MAX_NDIM))
+    if selem is None:
+        selem = np.ones((3,) * seed.ndim, dtype=bool)
+    else:
+        selem = _host(selem).astype(bool)
+    if selem.ndim != seed.ndim:
+        raise ValueError("selem must have the rank of the image")
+    if offset is None:
+        if not all(d % 2 == 1 for d in selem.shape):
+            raise ValueError("Footprint dimensions must all be odd")
+        offset = np.array([d // 2 for d in selem.shape])
+    else:
+        # (the reference compares offset.ndim with selem.ndim, which refuses every offset of a 2-D or larger element; what
+        # it means is one coordinate per axis of the element)
+        offset = np.ravel(_host(offset))
+        if len(offset) != selem.ndim:
+            raise ValueError("Offset and selem ndims must be equal.")
+        if not all(0 <= o < d for o, d in zip(offset, selem.shape)):
+            raise ValueError("Offset must be included inside selem")
+    offset = [int(o) for o in offset]
+
+    dtype = np.promote_types(seed.dtype, mask.dtype)
+    work = np.dtype(np.float32) if dtype == np.float16 else dtype      # exact: values are only compared and copied
+    core.dtype_code(work)
+    cur = seed.astype(work)                 # always a copy: the first buffer of the ping-pong, and the result when nothing moves
+    msk = core.ascontiguousarray(mask, work)
+    _rec_launches = 0
+    if cur.size == 0:
+        return cur.astype(dtype, copy=False)
+    other = core.empty(cur.shape, work)
+
+    st = np.ascontiguousarray(selem, dtype=np.uint8)
+    stp = st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+    sshape = S.c_int64s(st.shape)
+    offs = S.c_ints(offset)
+    lib = S.lib()
+    mdesc = msk._desc()
+    meth = 0 if method == "dilation" else 1
+
+    # the flag read-back schedule of the binary runs until stable (scipy/ndimage/morphology.py): the flags are read once per
+    # group of 1, 2, then 4 launches; launches queued after the image became stable reproduce it.  Word 1 of a launch's
+    # flags is the seed / mask order check, folded into the launch (the reference: a full-volume comparison and a
+    # synchronisation of its own before it starts).
+    flags = core.zeros((_REC_MAX_GROUP, 2), np.int32)
+    group = 1
+    while True:
+        if _rec_launches:
+            flags.fill(0)
+        for g in range(group):
+            a, b = cur._desc(), other._desc()
+            S.check(lib.mi_grey_reconstruction_step(ctypes.byref(a), ctypes.byref(b), ctypes.byref(mdesc), stp, sshape, offs,
+                                                    meth, ctypes.c_void_p(flags.ptr + 8 * g), None))
+            cur, other = other, cur
+            _rec_launches += 1
+        got = flags.get()
+        if got[:group, 1].any():
+            if method == "dilation":
+                raise ValueError("Intensity of seed image must be less than that of the mask image for reconstruction "
+                                 "by dilation.")
+            raise ValueError("Intensity of seed image must be greater than that of the mask image for reconstruction "
+                             "by erosion.")
+        if not got[:group, 0].all():
+            break
+        group = min(_REC_MAX_GROUP, group * 2)
+    return cur.astype(dtype, copy=False)
 
 
 # ---------------------------------------------------------------- structuring elements (selem.py)

@@ -463,6 +463,23 @@ int mi_binary_erosion_fused(const mi_array *in, const mi_array *out, const uint8
                             const int64_t *sshape, const int *origins, const mi_array *mask,
                             int border_value, int invert, int iterations, int32_t *changed_dev, mi_stream stream);
 
+/* One launch of grey-level morphological reconstruction (skimage.morphology.reconstruction; the reference runs its inner
+ * loop on the host, cupyimg/skimage/morphology/greyreconstruct.py:227-231).  With S = the offsets d = position - offsets of
+ * the true cells of `structure` (host uint8 prod(sshape); the cell at `offsets` itself is ignored), `out` is `in` moved
+ * towards the fixed point of
+ *     R[q] <- min(mask[q], max(R[q], max over d in S of R[q - d]))         method 0, dilation
+ *     R[q] <- max(mask[q], min(R[q], min over d in S of R[q - d]))         method 1, erosion
+ * (positions outside the array contribute nothing).  The operator is monotone: repeating launches (in -> out, ping-pong)
+ * until flags_dev[0] stays 0 reaches the unique fixed point, bit for bit, whatever a launch does inside.  2-D / 3-D arrays
+ * of uint8 / int16 / uint16 / float32 with the 3^n box or the connectivity-1 cross centred on its middle: every workgroup
+ * relaxes a block of the array in LDS until nothing inside it changes (csrc/reconstruct.hip: greyrec3_kernel), its halo being
+ * what the neighbours held when the launch began; anything else: one step of the rule per launch.  in, out, mask:
+ * C-contiguous, one shape, one dtype; out overlaps neither.  flags_dev: device int32[2], zeroed by the caller; [0] is OR-ed
+ * with 1 when a voxel of out differs from in, [1] when in > mask (erosion: in < mask) somewhere.  float16: MI_ERR_UNSUPPORTED
+ * with nothing queued (the caller converts to float32, which is exact for an operation that only compares and copies). */
+int mi_grey_reconstruction_step(const mi_array *in, const mi_array *out, const mi_array *mask, const uint8_t *structure,
+                                const int64_t *sshape, const int *offsets, int method, int32_t *flags_dev, mi_stream stream);
+
 /* ------------------------------------------------------------------ */
 /* K5: interpolation, spline order 0 and 1                              */
 /* ------------------------------------------------------------------ */

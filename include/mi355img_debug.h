@@ -95,6 +95,7 @@ int mi_debug_set_cubic_zfactor(int on);       /* order-3 affine, stream axis dec
 int mi_debug_set_stream_nt(int k);             /* non-temporal staging of rows no other workgroup reads (sep3d_long3 <= 9 taps, mm3f32_long, mm3u8_split <= 5): -1 by volume size (default), 0 never, 1 always */
 int mi_debug_set_pipe_normal_priority(int on); /* slab pipeline: comm stream at normal instead of high priority (read by mi_slab_pipe_create) */
 int mi_debug_set_label_generic(int on);       /* csrc/label.hip: 1 = every label call takes the generic union-find (one thread per voxel, global atomics), 0 = rank 2 / 3 binary labelling on the LDS tile kernel (default) */
+int mi_debug_set_reconstruct(int block_z, int block_y, int force_generic);   /* csrc/reconstruct.hip: planes / rows of greyrec3_kernel's blocks (0 = the planner's choice); force_generic = 1: every call takes greyrec_generic_kernel (one step of the rule per launch) */
 
 #ifdef __cplusplus
 }
