@@ -480,6 +480,38 @@ int mi_binary_erosion_fused(const mi_array *in, const mi_array *out, const uint8
 int mi_grey_reconstruction_step(const mi_array *in, const mi_array *out, const mi_array *mask, const uint8_t *structure,
                                 const int64_t *sshape, const int *offsets, int method, int32_t *flags_dev, mi_stream stream);
 
+/* One iteration of Chambolle's projection algorithm for total-variation denoising (skimage.restoration.denoise_tv_chambolle;
+ * the reference runs an iteration as about 25 whole-array operations and synchronises with the host for its stopping test,
+ * cupyimg/skimage/restoration/_denoise.py:44-86).  Two launches are queued: the iteration kernel and a one-workgroup energy /
+ * stop step; nothing synchronises.  With tau = 1 / (2 * image.ndim), T the image dtype and all arithmetic in T, products and
+ * sums rounded one by one:
+ *     d(q)   = -((p_0(q) + p_1(q)) + ...), then for a = 0, 1, ...: d += p_a(q - e_a) where q_a >= 1
+ *     out(q) = image(q) + d(q);   g_a(q) = out(q + e_a) - out(q) where q_a < n_a - 1, else 0
+ *     norm   = sqrt((g_0 g_0 + g_1 g_1) + ...);   den = norm * T(tau / weight) + 1;   p_out_a = (p_in_a - T(tau) g_a) / den
+ *     E_i    = (sum d d + weight * sum norm) / image.size        both sums and E in double, in an order fixed by the shape
+ * image: C-contiguous float32 / float64 of rank 1 .. MI_MAX_NDIM.  p_in, p_out: C-contiguous (image.ndim, image.size) arrays of
+ * the image's dtype, component a of voxel q at [a][q]; the caller zeroes p_in before iteration 0 and swaps the two between
+ * calls; p_out may hold anything (every element is written) and is not p_in.  work_dev: MI_TV_WORK_BYTES of device memory
+ * that one run of the algorithm keeps to itself.  Its first MI_TV_STATE_BYTES are the state block, zeroed by the caller
+ * before iteration 0: int32 stopped, int32 stop_iter, int32 done (iterations that ran), int32 unused, double E_prev, double
+ * E_0, double E of the last iteration that ran; the rest holds the workgroups' partial sums and needs no initialisation.
+ * `iteration` counts from 0.  The stop step of iteration i >= 1 sets stopped = 1 and stop_iter = i when
+ * |E_prev - E_i| < eps * E_0, else E_prev = E_i.  Every launch queued after that reads `stopped` first and touches nothing, so
+ * the caller may queue iterations in batches and read the state block once per batch.  After a stop the p to use (the
+ * reference returns `out` as computed at the start of the iteration that stopped, _denoise.py:55,82-87) is the p_in of
+ * iteration stop_iter, that is the buffer that was p_in in every call with iteration = stop_iter mod 2; the same holds for
+ * the last iteration when the loop runs out.  2-D and 3-D arrays: a fused kernel that streams along axis 0 with `out` in a
+ * two-plane window in LDS and reads image and p_in once, tile halos apart (csrc/tv_chambolle.hip: tv_fused_kernel); other
+ * ranks: one thread per voxel.  Other dtypes: MI_ERR_UNSUPPORTED with nothing queued (the caller converts). */
+#define MI_TV_STATE_BYTES 64
+#define MI_TV_MAX_PARTIALS 65536
+#define MI_TV_WORK_BYTES (MI_TV_STATE_BYTES + 16 * MI_TV_MAX_PARTIALS)
+int mi_tv_chambolle_step(const mi_array *image, const mi_array *p_in, const mi_array *p_out, double weight, double eps,
+                         int iteration, void *work_dev, mi_stream stream);
+/* out = image + d(p), d as above: the denoised image for a given dual field.  out: C-contiguous, the image's shape and dtype,
+ * overlaps neither image nor p. */
+int mi_tv_chambolle_output(const mi_array *image, const mi_array *p, const mi_array *out, mi_stream stream);
+
 /* ------------------------------------------------------------------ */
 /* K5: interpolation, spline order 0 and 1                              */
 /* ------------------------------------------------------------------ */
