@@ -134,6 +134,10 @@ SIGNATURES = {
     "mi_grey_reconstruction_step": [_arr, _arr, _arr, _u8p, _i64p, _ip, _i, _vp, _vp],
     "mi_tv_chambolle_step": [_arr, _arr, _arr, _d, _d, _i, _vp, _vp],
     "mi_tv_chambolle_output": [_arr, _arr, _arr, _vp],
+    "mi_hessian_matrix": [_arr, _arr, _i, _vp],
+    "mi_symmetric_eigvals": [_arr, _arr, _i, _vp],
+    "mi_ridge_fill_nonpositive": [_arr, _d, _vp],
+    "mi_ridge_scale": [_arr, _arr, _i, _i, _d, _d, _d, _d, _arr, _vp, _vp],
     "mi_map_coordinates": [_arr, _arr, _arr, _i, _i, _d, _vp],
     "mi_affine_transform": [_arr, _arr, _dp, _i, _i, _d, _vp],
     "mi_spline_pad": [_arr, _arr, _i, _i, _d, _vp],

@@ -512,6 +512,49 @@ int mi_tv_chambolle_step(const mi_array *image, const mi_array *p_in, const mi_a
  * overlaps neither image nor p. */
 int mi_tv_chambolle_output(const mi_array *image, const mi_array *p, const mi_array *out, mi_stream stream);
 
+/* The Hessian family (skimage.feature.hessian_matrix / hessian_matrix_eigvals, skimage.filters.frangi / sato / meijering;
+ * cupyimg/skimage/feature/corner.py:141-211, 260-309, cupyimg/skimage/filters/ridges.py:112-533): what follows the Gaussian
+ * of one scale.  All arithmetic in the dtype T of the smoothed array g (float32 / float64, C-contiguous, rank 1 ..
+ * MI_MAX_NDIM, at least 2 samples along every axis), products and sums rounded one by one.
+ *
+ * mi_hessian_matrix: out[e] = gradient(gradient(g)[a0], axis = a1), numpy.gradient with unit spacing and edge_order 1
+ * ((f[i+1] - f[i-1]) / 2 inside, f[1] - f[0] and f[n-1] - f[n-2] at the ends, applied twice), for the e-th pair (a0, a1) of
+ * combinations_with_replacement(axes, 2), axes = ndim-1 .. 0 (order_xy = 0, the reference's order "rc") or 0 .. ndim-1
+ * (order_xy = 1, "xy"); bit-identical to NumPy on the same g.  out: C-contiguous (ndim (ndim + 1) / 2, g.size) of g's dtype.
+ * Rank 2 and 3: one launch that stages tiles of g with a two-sample halo in LDS (one read of g, 3 or 6 writes); other ranks
+ * one thread per voxel.
+ *
+ * mi_symmetric_eigvals: the eigenvalues, decreasing, of the symmetric ndim x ndim matrices whose upper triangles, row by row,
+ * are elems[0 .. ndim (ndim + 1) / 2) (each of `size` values): out C-contiguous (ndim, size) of the same dtype.  2 x 2: the
+ * reference's closed form operation by operation; larger: cyclic Jacobi, every eigenvalue within a few eps * ||A||_F of the
+ * exact one (LAPACK is not bit-reproduced).
+ *
+ * mi_ridge_scale: Hessian elements in "rc" order from g, times T(sigma^2), eigenvalues, ordering and one of
+ *   MI_RIDGE_EIGENVALUES  out: (ndim, g.size) of g's dtype, the eigenvalues ordered by `sorting` (NONE = decreasing, VAL =
+ *                         increasing, ABS = stable sort of the decreasing list by magnitude)
+ *   MI_RIDGE_FRANGI       p0, p1, p2 = 2 alpha^2, 2 beta^2, 2 gamma^2; 2-D and 3-D
+ *   MI_RIDGE_SATO         2-D and 3-D
+ *   MI_RIDGE_MEIJERING    p0 = alpha; scratch: a volume of g's shape and dtype that receives aux; work_dev: 8 bytes the
+ *                         caller set to 0xff before the call, afterwards the order-preserving key of min(aux) (a double's
+ *                         bits, inverted when negative, else with the sign bit set); a second launch normalises by that
+ *                         minimum read on the device
+ * for the three responses out is float64 of g's shape and is updated in place: out = max(out, response).  2-D and 3-D: one
+ * launch from the staged tile with nothing but out written; other ranks, or after mi_debug_set_ridges(.., .., 1): the
+ * elements in pool memory, then one thread per voxel -- the same arithmetic, the same bits. */
+#define MI_RIDGE_EIGENVALUES 0
+#define MI_RIDGE_FRANGI 1
+#define MI_RIDGE_SATO 2
+#define MI_RIDGE_MEIJERING 3
+#define MI_RIDGE_SORT_NONE 0
+#define MI_RIDGE_SORT_VAL 1
+#define MI_RIDGE_SORT_ABS 2
+int mi_hessian_matrix(const mi_array *g, const mi_array *out, int order_xy, mi_stream stream);
+int mi_symmetric_eigvals(const mi_array *elems, const mi_array *out, int ndim, mi_stream stream);
+int mi_ridge_scale(const mi_array *g, const mi_array *out, int kind, int sorting, double sigma, double p0, double p1, double p2,
+                   const mi_array *scratch, void *work_dev, mi_stream stream);
+/* a[a <= 0] = value in place (the last step of skimage.filters.hessian, ridges.py:634); a: C-contiguous float64 */
+int mi_ridge_fill_nonpositive(const mi_array *a, double value, mi_stream stream);
+
 /* ------------------------------------------------------------------ */
 /* K5: interpolation, spline order 0 and 1                              */
 /* ------------------------------------------------------------------ */
