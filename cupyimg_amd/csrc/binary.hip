@@ -90,6 +90,7 @@ binary3_kernel(const T *__restrict__ in, void *__restrict__ out, int out_dt, con
 }  // namespace mi
 
 namespace mi {
+void note_kernel(const char *fmt, ...);      // separable3d.hip: which kernel a call dispatched (mi_debug_last_kernel)
 int binary3_tiled(const mi_array *in, const mi_array *out, const uint8_t *structure, const int64_t *sshape,
                   const int *origins, const mi_array *mask, int border_value, int invert, int32_t *changed,
                   hipStream_t s);   // binary3d.hip
@@ -213,6 +214,10 @@ extern "C" int mi_binary_erosion(const mi_array *in, const mi_array *out, const 
     dim3 grid;
     grid_for(total, 256, &grid);
     const uint8_t *mp = mask ? (const uint8_t *)mask->data : nullptr;
+    static const char *const tname[] = {"bool", "int8", "uint8", "int16", "uint16", "int32", "uint32", "int64", "uint64", "float", "double"};
+    if (in->dtype >= MI_BOOL && in->dtype <= MI_F64)
+        note_kernel(fast3 ? "mi::binary3_kernel<%s> (one thread per voxel, one iteration)" : "mi::binary_erosion_kernel<%s,%d> (one thread per voxel, one iteration)",
+                    tname[in->dtype], in->ndim <= 3 ? 3 : MI_MAX_NDIM);
     return dispatch_dtype(in->dtype, [&]<typename T>() -> int {
         const T *ip = (const T *)in->data;
         if (fast3) {

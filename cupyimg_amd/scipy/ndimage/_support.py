@@ -123,17 +123,20 @@ def float16_aware(fn):
         out = ba.get("output", None)
         out_arr = out if isinstance(out, core.ndarray) and _is_f16(out) else None
         out16 = out_arr is not None or (out is not None and not isinstance(out, core.ndarray) and _is_f16(out))
+        if out_arr is not None:
+            # an ARRAY stays an array (functions that return None for one, or ignore a mere dtype, keep doing so)
+            tmp = ba["output"] = core.empty(out_arr.shape, np.float32)
+            res = fn(*bound.args, **bound.kwargs)
+            out_arr[...] = tmp
+            return out_arr if res is tmp else res
         if out16:
             ba["output"] = np.float32
         res = fn(*bound.args, **bound.kwargs)
         if not isinstance(res, core.ndarray):
             return res
-        if out_arr is not None:
-            out_arr[...] = res
-            return out_arr
-        # no `output` given: functions whose result takes the input dtype (now float32) give float16 back; the
-        # others (bool masks of binary morphology, float64 spline coefficients) keep their own default
-        if out16 or (out is None and in16 and res.dtype == np.float32):
+        # functions whose result takes the requested / the input dtype (now float32) give float16 back; the others
+        # (bool masks of binary morphology, which ignore a dtype as SciPy does; float64 spline coefficients) keep their own
+        if res.dtype == np.float32 and (out16 or (out is None and in16)):
             return res.astype(np.float16)
         return res
     return wrapper

@@ -94,6 +94,55 @@ def _minkowski_root(structure):
     return _ROOTS[key]
 
 
+def _run_until_stable(launch_fill, launch_fused, launch, bufs, cur, read_flags, max_group, kb):
+    """The host loop of an erosion / dilation that runs until nothing changes; returns the array that holds the result.
+
+    `launch_fill(src, dst, g)` (or None), `launch_fused(src, dst, kb, g)` and `launch(src, dst, g)` take one step from `src` into
+    `dst` and write their "changed" flags into row `g` of the flag table: fill and single launches one flag in column 0, a
+    fused launch one flag per iteration in columns `:kb`.  The first two return False when the library refuses the arrays;
+    `launch` never refuses.  `bufs` are the two buffers the steps alternate between, the first step goes from `cur` into
+    `bufs[1]`.  `read_flags()` returns the table on the host and clears it on the device; it is called once per group of 1, 2,
+    4, ... `max_group` launches.
+
+    The first launch decides the mode ("fill" | "fused" | "single").  The launches alternate src -> bufs[1] -> bufs[0] -> ...,
+    so a later launch sees OTHER arrays than the first and may be refused where the first was taken (an output that is not
+    16-byte aligned, a ragged row without readable slack behind it): the refused step is then taken as a single launch into the
+    same `dst`, and the run stays in single mode.  Every pass of the loop therefore launches at least one step."""
+    group = 1
+    which = 1
+    mode = None
+    while True:
+        cols = []                                     # flag columns to read of every launch of this group
+        for g in range(group if mode != "single" else 1):
+            dst = bufs[which]
+            if mode is None:
+                if launch_fill is not None and launch_fill(cur, dst, g):
+                    mode = "fill"
+                elif launch_fused(cur, dst, kb, g):
+                    mode = "fused"
+                else:
+                    mode = "single"
+                    launch(cur, dst, g)
+            elif mode == "fill" and launch_fill(cur, dst, g):
+                pass
+            elif mode == "fused" and launch_fused(cur, dst, kb, g):
+                pass
+            else:
+                mode = "single"
+                launch(cur, dst, g)
+            cols.append(kb if mode == "fused" else 1)
+            cur = dst
+            which ^= 1
+            if mode == "single":
+                break
+        assert cols, "a pass of the until-stable loop launched nothing"
+        got = read_flags()
+        # the first iteration that changes nothing ends the run; the later ones of its group reproduce the same volume
+        if any(not got[g, :c].all() for g, c in enumerate(cols)):
+            return cur
+        group = min(max_group, group * 2)
+
+
 def _binary_erosion(input, structure, iterations, mask, output, border_value, origin, invert,
                     brute_force=True):
     """morphology.py:204-331"""
@@ -248,44 +297,21 @@ def _binary_erosion(input, structure, iterations, mask, output, border_value, or
                 S.check(rc)
                 return True
 
-            group = 1
-            kb = _MAX_FUSED_UNTIL_STABLE
             flags = core.zeros((_MAX_GROUP, _MAX_FUSED_UNTIL_STABLE), np.int32)
-            which = 1
-            mode = None                                   # "fill" | "fused" | "single"
-            while True:
-                flags.fill(0)
-                launched = 0
-                for g in range(group if mode != "single" else 1):
-                    dst = bufs[which]
-                    fptr = ctypes.c_void_p(flags.ptr + 4 * _MAX_FUSED_UNTIL_STABLE * g)
-                    if mode is None:
-                        if invert and mdesc is not None and launch_fill(cur, dst, fptr):
-                            mode = "fill"
-                        elif launch_fused(cur, dst, kb, fptr):
-                            mode = "fused"
-                        else:
-                            mode = "single"
-                            launch(cur, dst, fptr)
-                    elif mode == "fill":
-                        if not launch_fill(cur, dst, fptr):
-                            break                          # (cannot happen: same arrays, same answer)
-                    elif mode == "fused":
-                        if not launch_fused(cur, dst, kb, fptr):
-                            break
-                    else:
-                        launch(cur, dst, fptr)
-                    cur = dst
-                    which ^= 1
-                    launched += 1
+
+            def slot(g):
+                return ctypes.c_void_p(flags.ptr + 4 * _MAX_FUSED_UNTIL_STABLE * g)
+
+            def read_flags():
                 got = flags.get()
-                if mode == "fused":
-                    stable = not got[:launched, :kb].all()
-                else:
-                    stable = not got[:launched, 0].all()
-                if stable:
-                    break
-                group = min(_MAX_GROUP, group * 2)
+                flags.fill(0)
+                return got
+
+            cur = _run_until_stable(
+                (lambda s_, d_, g: launch_fill(s_, d_, slot(g))) if invert and mdesc is not None else None,
+                lambda s_, d_, k, g: launch_fused(s_, d_, k, slot(g)),
+                lambda s_, d_, g: launch(s_, d_, slot(g)),
+                bufs, cur, read_flags, _MAX_GROUP, _MAX_FUSED_UNTIL_STABLE)
         if cur is not final:
             final[...] = cur
     if not direct:

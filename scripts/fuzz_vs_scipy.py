@@ -1,5 +1,5 @@
 """Randomised differential test of the HIP path against scipy.ndimage (run on the GPU box).
-usage: python scripts/fuzz_vs_scipy.py [--ranges | --measure] [seconds] [seed] [max cases]   -- prints mismatches with
+usage: python scripts/fuzz_vs_scipy.py [--ranges | --measure | --binary] [seconds] [seed] [max cases]   -- prints mismatches with
 their parameters.
 env FUZZ_ONLY=op1,op2 restricts the op families, FUZZ_TRACE=1 prints every case before it runs.
 --ranges: a separate draw on the value ranges of real scans (MR 0 .. 4095, CT Hounsfield units with padding, 1e4 + noise,
@@ -12,7 +12,14 @@ reduction (tests/helpers/measure_ref.py: the value ranges above with +-0, +-inf 
 None / scalar / list / host / device array with duplicates, absent, 0 and negative values, slot counts around the LDS
 limits and index ranges either side of the lookup-table threshold).  Reductions are judged against a host float64
 reference with the bounds derived in measure_ref's docstring, exact where the result is an integer, an extreme, a
-position or a sum of integers; result type, shape, dtype and exceptions against SciPy."""
+position or a sum of integers; result type, shape, dtype and exceptions against SciPy.
+--binary: a separate draw of binary morphology on real masks (tests/helpers/binary_ref.py draw_case: every binary_*
+function, ranks 1-5, every input dtype with NaN / inf / -0.0 / subnormals / values that are zero in their low byte,
+structures of every kind, origins, masks of several dtypes, iteration counts up to 13 and runs until stable, every form
+of `output`, strided and transposed inputs).  Results are judged bit for bit against the plain NumPy reference of that
+module (itself checked against SciPy by tests/test_binary_yardstick.py), together with the dtype, the return value and
+the bytes between the samples of a strided output; where the reference raises, the exception type against SciPy's.
+No case is skipped."""
 import os, sys, time, traceback
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 RANGES = "--ranges" in sys.argv
@@ -21,6 +28,9 @@ if RANGES:
 MEASURE = "--measure" in sys.argv
 if MEASURE:
     sys.argv.remove("--measure")
+BINARY = "--binary" in sys.argv
+if BINARY:
+    sys.argv.remove("--binary")
 import numpy as np
 import scipy.ndimage as sndi
 import cupyimg_amd as ca
@@ -394,10 +404,56 @@ def run_measure():
     return fails
 
 
+def run_binary():
+    import warnings
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from helpers import binary_ref as br
+    warnings.simplefilter("ignore")
+    t_end = time.time() + budget
+    n = fails = 0
+    counts = {}
+    while time.time() < t_end and n < max_cases:
+        case = br.draw_case(rng)
+        n += 1
+        counts[case["func"]] = counts.get(case["func"], 0) + 1
+        if os.environ.get("FUZZ_TRACE"):
+            print("TRACE", case["desc"], flush=True)
+        want = want_exc = got_exc = None
+        try:
+            want = br.reference(case)
+        except Exception as e:
+            want_exc = e
+        try:
+            ret, out, base = br.call(ndi, case, ca.asarray)
+        except Exception as e:
+            got_exc = e
+        if want_exc is not None:
+            # the reference refuses: SciPy decides what the call should have done
+            try:
+                sret, sout, sbase = br.call(sndi, case, f16_as_f32=True)
+                ok = got_exc is None
+                why = "SciPy answers, the reference raised %r" % (want_exc,)
+                if ok:
+                    ok, why = br.judge(case, br.truth(br.to_host(sout if sout is not None else sret)), ret, out, base)
+            except Exception as se:
+                ok, why = type(got_exc) is type(se), "raised %r, SciPy %r" % (got_exc, se)
+        elif got_exc is not None:
+            ok, why = False, "raised %r" % (got_exc,)
+        else:
+            ok, why = br.judge(case, want, ret, out, base)
+        if not ok:
+            fails += 1
+            print("MISMATCH", case["desc"], why, "kernel", ca.last_kernel(), flush=True)
+    print("binary: cases %d, failures %d, per op %s" % (n, fails, counts))
+    return fails
+
+
 if RANGES:
     sys.exit(1 if run_ranges() else 0)
 if MEASURE:
     sys.exit(1 if run_measure() else 0)
+if BINARY:
+    sys.exit(1 if run_binary() else 0)
 
 t_end = time.time() + budget
 n = fails = skipped = 0

@@ -223,3 +223,106 @@ def test_minkowski_root_of_cubes_and_octahedra():
     ball = (ball ** 2).sum(0) <= 4
     for st in (ball, np.ones((3, 3, 3), bool), np.ones((5, 5, 3), bool), np.ones((4, 4, 4), bool), np.ones((5, 5), bool)):
         assert morphology._minkowski_root(st) == (None, 1)
+
+
+# ---- the until-stable driver of binary morphology (morphology._run_until_stable) on NumPy stand-ins for the launchers ----
+class _StubLaunchers:
+    """One reference iteration per step on host arrays, flags written as the kernels write them (single and fill launches:
+    column 0 of their row; a fused launch: one flag per iteration in columns :kb).  `refuse(call number, dst)` says which
+    fill / fused calls the library would refuse.  Every call counts; past `cap` the stub raises, so a driver that spins
+    fails instead of hanging."""
+
+    def __init__(self, offsets, mask, kb, group, cap, refuse):
+        from helpers import binary_ref as br
+        self.step = lambda a: br.step(a, offsets, 0, mask, True)
+        self.flags = np.zeros((group, kb), np.int32)
+        self.cap, self.refuse = cap, refuse
+        self.calls = self.refusable = 0
+        self.kinds = []
+
+    def _count(self, kind):
+        self.calls += 1
+        self.kinds.append(kind)
+        if self.calls > self.cap:
+            raise AssertionError("more than %d launches: %s ..." % (self.cap, self.kinds[:12]))
+
+    def _refused(self, dst):
+        self.refusable += 1
+        return self.refuse(self.refusable, dst)
+
+    def _iterate(self, src, dst, g, n):
+        cur = src.copy()
+        for i in range(n):
+            nxt = self.step(cur)
+            self.flags[g, i] |= int((nxt != cur).any())
+            cur = nxt
+        dst[...] = cur
+
+    def single(self, src, dst, g):
+        self._count("single")
+        self._iterate(src, dst, g, 1)
+
+    def fill(self, src, dst, g):
+        self._count("fill")
+        if self._refused(dst):
+            return False
+        self._iterate(src, dst, g, 1)
+        return True
+
+    def fused(self, src, dst, k, g):
+        self._count("fused")
+        if self._refused(dst):
+            return False
+        self._iterate(src, dst, g, k)
+        return True
+
+    def read_flags(self):
+        got = self.flags.copy()
+        self.flags[...] = 0
+        return got
+
+
+def _until_stable_problem():
+    """a propagation along a winding corridor: 41 iterations to the fixed point"""
+    from helpers import binary_ref as br
+    mask = np.zeros((9, 12), bool)
+    mask[::2, :] = True
+    mask[1::4, -1] = True
+    mask[3::4, 0] = True
+    seed = np.zeros_like(mask)
+    seed[0, 0] = True
+    count = []
+    want = br.propagation(seed, mask=mask, count=count)
+    assert want.sum() == mask.sum() and count[0] >= 40
+    return seed, mask, br.dilation_offsets(br.generate_binary_structure(2, 1), 0), want, count[0]
+
+
+_REFUSALS = {
+    "never": lambda n, dst, final: False,
+    "the first call": lambda n, dst, final: n == 1,
+    "from the 2nd call on": lambda n, dst, final: n >= 2,
+    "every other call": lambda n, dst, final: n % 2 == 0,
+    "when dst is the caller's buffer": lambda n, dst, final: dst is final,
+}
+
+
+@pytest.mark.parametrize("with_fill", [False, True], ids=["fused", "fill"])
+@pytest.mark.parametrize("refusal", list(_REFUSALS))
+def test_until_stable_driver_ends_whatever_the_library_refuses(refusal, with_fill):
+    """The launches alternate src -> other -> final -> other ...: a launch into the caller's buffer (unaligned, say) can be
+    refused where the first one was taken.  Every pattern of refusals ends, at the fixed point of the reference operator,
+    within (true iteration count + batch x group) launches."""
+    seed, mask, offsets, want, true_count = _until_stable_problem()
+    kb, group = 4, 4
+    final, other = np.zeros_like(seed), np.zeros_like(seed)
+    stub = _StubLaunchers(offsets, mask, kb, group, true_count + kb * group, lambda n, dst: _REFUSALS[refusal](n, dst, final))
+    res = morphology._run_until_stable(stub.fill if with_fill else None, stub.fused, stub.single, [final, other], seed,
+                                       stub.read_flags, group, kb)
+    assert res is final or res is other
+    assert np.array_equal(res, want), (refusal, stub.kinds)
+    assert stub.calls <= true_count + kb * group
+    if refusal == "never":
+        assert set(stub.kinds) == {"fill" if with_fill else "fused"}
+    if refusal == "when dst is the caller's buffer":
+        # the first launch (into `other`) is taken, the second is refused and repeated as a single launch, single from there on
+        assert stub.kinds[1] == stub.kinds[0] and set(stub.kinds[2:]) == {"single"}, stub.kinds
