@@ -81,6 +81,7 @@ SOURCES = [
     ("reconstruct.hip", []),
     ("tv_chambolle.hip", ["-ffp-contract=off"]),
     ("ridges.hip", ["-ffp-contract=off"]),
+    ("exposure.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function",
           "-I" + os.path.join(os.path.dirname(HERE), "include")]

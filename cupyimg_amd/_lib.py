@@ -138,6 +138,11 @@ SIGNATURES = {
     "mi_symmetric_eigvals": [_arr, _arr, _i, _vp],
     "mi_ridge_fill_nonpositive": [_arr, _d, _vp],
     "mi_ridge_scale": [_arr, _arr, _i, _i, _d, _d, _d, _d, _arr, _vp, _vp],
+    "mi_clahe_maps": [_arr, _ip, _d, _d, _i, ctypes.c_int64, _arr, _vp],
+    "mi_clahe_apply": [_arr, _ip, _d, _d, _i, _arr, _arr, _vp, _vp],
+    "mi_clahe_finish": [_arr, _arr, _vp, _vp],
+    "mi_interp_map": [_arr, _arr, _arr, _arr, _vp],
+    "mi_rescale_intensity": [_arr, _arr, _d, _d, _d, _d, _vp],
     "mi_map_coordinates": [_arr, _arr, _arr, _i, _i, _d, _vp],
     "mi_affine_transform": [_arr, _arr, _dp, _i, _i, _d, _vp],
     "mi_spline_pad": [_arr, _arr, _i, _i, _d, _vp],

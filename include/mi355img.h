@@ -555,6 +555,70 @@ int mi_ridge_scale(const mi_array *g, const mi_array *out, int kind, int sorting
 /* a[a <= 0] = value in place (the last step of skimage.filters.hessian, ridges.py:634); a: C-contiguous float64 */
 int mi_ridge_fill_nonpositive(const mi_array *a, double value, mi_stream stream);
 
+/* skimage.exposure.equalize_adapthist (contrast limited adaptive histogram equalisation, cupyimg/skimage/exposure/
+ * _adapthist.py:86-275) as three launches without a host round trip; the reference pads the image, gathers every contextual
+ * region into a 2-D array, clips the histograms in a Python loop on the host and blends in 2^ndim rounds of whole-array
+ * operations.  Bit-identical to it.  With s_a the shape, k_a the kernel size, K = prod(k), every floating-point operation
+ * rounded on its own (the source is compiled without contraction):
+ *   1  u = img_as_uint(image): uint8 x 257; uint16 as it is; floats uint16(clip(rint(x * 65535), 0, 65535)) in the image dtype
+ *   2  g = uint16(rint((clip(u, umin, umax) - umin) / (umax - umin) * 16383.0 + 0.0)) in float64, umin and umax over the whole
+ *      image; min(u, 16383) when umin == umax
+ *   3  b = g // (1 + 16384 // nbins)
+ *   4  contextual regions of side k_a aligned to the image origin, ceil(s_a / k_a) per axis (the reference's int(S_a / k_a) - 1
+ *      on its padded shape S_a = k_a (ceil(s_a / k_a) + 1)); a region that ends beyond the image reads b at the reflected
+ *      index (numpy.pad "reflect": period 2 (s_a - 1), an axis of length 1 repeats its sample); nothing is padded in memory
+ *   5  per region h = the nbins-bin histogram of b, clipped at `clip_limit`:
+ *        E = sum max(h - c, 0); h = min(h, c); incr = E // nbins; upper = c - incr
+ *        where h < upper: h += incr, E -= incr;  then where upper <= h < c: E -= c - h, h = c
+ *        while E > 0: E0 = E; for index = 0 .. nbins - 1: step = max(1, #(h < c) // E); the bins index, index + step, ...
+ *        that are below c gain 1 each and E loses their number; the round ends when E <= 0 (E may go below 0); the loop
+ *        ends after a round that changed nothing
+ *   6  map = int64(min(float64(cumsum(h)) * (16383 / K) + 0, 16383))
+ *   7  voxel i: p_a = i_a + k_a // 2, cell B_a = p_a // k_a, j_a = p_a % k_a, c_a = j_a / k_a in float64.  For every corner e in
+ *      itertools.product((0, 1), repeat = ndim) order: region r_a = clip(B_a - 1 + e_a, 0, regions_a - 1), weight w_a = c_a
+ *      where e_a = 1, else 1 - c_a; term = float32(float64(map_r[b(i)]) * ((w_(n-1) * w_(n-2)) * ... * w_0)); the terms are
+ *      added in float32 in that order; v = uint16(sum), truncated
+ *   8  f = float64(v) * (1.0 / 65535); out = (f - fmin) / (fmax - fmin) * 1.0 + 0.0 with fmin, fmax over the whole array, f
+ *      itself when they are equal
+ * image: C-contiguous uint8 / uint16 / float32 / float64 of rank 1 .. MI_CLAHE_MAX_NDIM (other dtypes: MI_ERR_UNSUPPORTED,
+ * nothing queued); kernel: host int[ndim], each at least 1, prod(kernel) at most 2^30; umin, umax: the extrema of u (step 1 of
+ * the image's extrema: the conversion is monotone); nbins 1 .. MI_CLAHE_GRAY; maps: C-contiguous uint16 (regions, nbins),
+ * regions in row-major order.
+ *
+ * mi_clahe_maps (steps 1 - 6): one workgroup per region histograms in LDS (a histogram per wave up to 1024 bins, merged before
+ * the clip; one shared histogram above that, or after mi_debug_set_clahe(.., 1)), clips with one workgroup reduction per stage
+ * and per strided pass, and writes the region's row of maps.  clip_limit: 1 .. prod(kernel).
+ * mi_clahe_apply (steps 1 - 3, 7): out: C-contiguous uint16 of the image's shape, receives v.  work_dev: MI_CLAHE_WORK_BYTES of
+ * device memory the caller set to 0xff; afterwards uint32 [0] = min v, [1] = 65535 - max v (one pair of atomics per
+ * workgroup).  Rank 2 and 3 with (nbins << ndim) * 2 <= 65536 bytes of mappings and sum(kernel) <= 1024: a workgroup per slab of
+ * an interpolation cell with the cell's 2^ndim mappings and the coefficients in LDS; otherwise, or after
+ * mi_debug_set_clahe(1, ..): one thread per voxel, mappings from global memory -- the same arithmetic, the same bits.
+ * mi_clahe_finish (step 8): v uint16, out float64, both C-contiguous of one shape; reads work_dev on the device. */
+#define MI_CLAHE_MAX_NDIM 4
+#define MI_CLAHE_GRAY 16384
+#define MI_CLAHE_WORK_BYTES 16
+int mi_clahe_maps(const mi_array *image, const int *kernel, double umin, double umax, int nbins, int64_t clip_limit,
+                  const mi_array *maps, mi_stream stream);
+int mi_clahe_apply(const mi_array *image, const int *kernel, double umin, double umax, int nbins, const mi_array *maps,
+                   const mi_array *out, void *work_dev, mi_stream stream);
+int mi_clahe_finish(const mi_array *v, const mi_array *out, const void *work_dev, mi_stream stream);
+
+/* out = numpy.interp(image, xp, fp) in float64: with j the last knot at or below x, fp[j] + ((fp[j+1] - fp[j]) / (xp[j+1] -
+ * xp[j])) * (x - xp[j]), slope times difference first; fp[0] below xp[0], fp[n-1] above xp[n-1], fp[j] where x == xp[j]; NaN
+ * stays NaN (skimage.exposure.equalize_hist, for which the reference pulls the image to the host, exposure.py:253-256).
+ * image: C-contiguous uint8 / uint16 / float32 / float64; xp (increasing), fp: device float64 vectors of 1 ..
+ * MI_INTERP_MAX_KNOTS knots, staged in LDS up to 4096 knots, searched in global memory above; out: float64, the image's shape. */
+#define MI_INTERP_MAX_KNOTS 65536
+int mi_interp_map(const mi_array *image, const mi_array *xp, const mi_array *fp, const mi_array *out, mi_stream stream);
+
+/* skimage.exposure.rescale_intensity (exposure.py:439-463): x = clip(image, imin, imax), then ((x - imin) / (imax - imin)) *
+ * (omax - omin) + omin, every operation rounded on its own, in float32 for a float32 image (the four scalars and the two
+ * differences, formed in double, rounded to float32 first) and in float64 for every other dtype; with imin == imax only
+ * clip(x, omin, omax).  The result is converted to out's dtype by truncation.  image, out: C-contiguous, one shape, any
+ * dtype but float16. */
+int mi_rescale_intensity(const mi_array *image, const mi_array *out, double imin, double imax, double omin, double omax,
+                         mi_stream stream);
+
 /* ------------------------------------------------------------------ */
 /* K5: interpolation, spline order 0 and 1                              */
 /* ------------------------------------------------------------------ */
