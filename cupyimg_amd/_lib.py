@@ -143,6 +143,13 @@ SIGNATURES = {
     "mi_clahe_finish": [_arr, _arr, _vp, _vp],
     "mi_interp_map": [_arr, _arr, _arr, _arr, _vp],
     "mi_rescale_intensity": [_arr, _arr, _d, _d, _d, _d, _vp],
+    "mi_snake_acwe_init": [_arr, _arr, _vp, _vp],
+    "mi_snake_acwe_step": [_arr, _arr, _arr, _arr, _d, _d, _i, _i, _vp, _vp],
+    "mi_snake_gac_step": [_arr, _arr, _arr, _arr, _d, _i, _i, _i, _vp],
+    "mi_snake_curvature": [_arr, _arr, _arr, _i, ctypes.c_uint, _vp],
+    "mi_snake_order_stats": [_arr, ctypes.c_int64, ctypes.c_int64, _vp, _vp],
+    "mi_snake_binarize": [_arr, _arr, _i, _vp],
+    "mi_snake_inverse_gradient": [_arr, _arr, _d, _vp],
     "mi_map_coordinates": [_arr, _arr, _arr, _i, _i, _d, _vp],
     "mi_affine_transform": [_arr, _arr, _dp, _i, _i, _d, _vp],
     "mi_spline_pad": [_arr, _arr, _i, _i, _d, _vp],

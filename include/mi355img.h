@@ -619,6 +619,48 @@ int mi_interp_map(const mi_array *image, const mi_array *xp, const mi_array *fp,
 int mi_rescale_intensity(const mi_array *image, const mi_array *out, double imin, double imax, double omin, double omax,
                          mi_stream stream);
 
+/* Morphological snakes (skimage.segmentation.morphological_chan_vese / morphological_geodesic_active_contour, sup_inf, inf_sup;
+ * cupyimg/skimage/segmentation/morphsnakes.py:55-92, 347-378, 468-510; csrc/morphsnakes.hip).  The level set u is a C-contiguous
+ * int8 array of 0 and 1 of rank 2 or 3, the image a C-contiguous float32 / float64 array (T) of the same shape (other dtypes:
+ * MI_ERR_UNSUPPORTED with nothing queued, the caller converts).  An iteration is a chain of radius-1 stages; voxels outside the
+ * array count as 0 in the morphological ones:
+ *     dilate / erode  u' = OR / AND of u over the 3^ndim neighbourhood where double(image) > mask_threshold, else u
+ *     acwe    du_a = numpy.gradient(u) along axis a ((u[+1] - u[-1]) / 2 inside, one-sided differences at the two ends); where some
+ *             du_a != 0: b = T(lambda1) (I - c1)^2 - T(lambda2) (I - c0)^2 in T, b < 0: u' = 1, b > 0: u' = 0; else u' = u
+ *     gac     aux = ((0 + gI_0 du_0) + gI_1 du_1) + ..., gI = numpy.gradient(image), in T; aux > 0: u' = 1, aux < 0: u' = 0
+ *     SI      u' = OR over the 9 planes (rank 3) / 4 lines (rank 2) P of morphsnakes.py:33-49 of (AND of u over P)    (sup_inf)
+ *     IS      u' = AND over the same P of (OR of u over P)                                                             (inf_sup)
+ * Smoothing step number j of a call (j = `first`, first + 1, ... over the `smoothing` steps of this iteration) is SI o IS for even
+ * j and IS o SI for odd j.  The first launch of a chain runs the update stages and up to MI_SNAKE_FUSED_SMOOTHING smoothing
+ * steps on overlapped boxes in LDS, every further launch two smoothing steps; launches alternate between u_out and u_tmp and
+ * the last writes u_out.  u_in is only read; u_tmp (same shape, needed when the chain has more than one launch) is scratch.
+ * No launch depends on data: their number is a function of `smoothing` alone, and nothing synchronises.
+ * work_dev: MI_SNAKE_WORK_BYTES of device memory one run keeps to itself; its first MI_SNAKE_STATE_BYTES are the state block:
+ * double c0, c1 (the means outside and inside, rounded to T), double[4] the sums of image (1 - u), image u, (1 - u), u, double[2]
+ * the result of mi_snake_order_stats; the rest holds the workgroups' partial sums and needs no initialisation.
+ * mi_snake_acwe_init: the four sums of (image, u), in double in an order fixed by the shape, and c0 = T(sum image (1 - u)) /
+ * T(sum (1 - u) + 1e-8), c1 likewise, into the state block.  mi_snake_acwe_step: one iteration with the c0, c1 of the state
+ * block; its last launch accumulates the sums of the new u and a one-workgroup launch renews c0 and c1. */
+#define MI_SNAKE_STATE_BYTES 64
+#define MI_SNAKE_MAX_PARTIALS 65536
+#define MI_SNAKE_WORK_BYTES (MI_SNAKE_STATE_BYTES + 32 * MI_SNAKE_MAX_PARTIALS)
+#define MI_SNAKE_FUSED_SMOOTHING 2
+int mi_snake_acwe_init(const mi_array *image, const mi_array *u, void *work_dev, mi_stream stream);
+int mi_snake_acwe_step(const mi_array *image, const mi_array *u_in, const mi_array *u_out, const mi_array *u_tmp, double lambda1,
+                       double lambda2, int smoothing, int first, void *work_dev, mi_stream stream);
+/* One MorphGAC iteration: balloon > 0: a dilate stage first, balloon < 0: an erode stage, 0: none; then gac and the smoothing. */
+int mi_snake_gac_step(const mi_array *image, const mi_array *u_in, const mi_array *u_out, const mi_array *u_tmp, double mask_threshold,
+                      int balloon, int smoothing, int first, mi_stream stream);
+/* nops (1 .. 32) operators in a row, operator i = SI when bit i of ops is set, IS otherwise. */
+int mi_snake_curvature(const mi_array *u_in, const mi_array *u_out, const mi_array *u_tmp, int nops, unsigned ops, mi_stream stream);
+/* The order statistics number k0 and k1 (from 0) of a C-contiguous float32 / float64 array, as doubles at bytes 48 .. 63 of the
+ * state block: a radix select over order-preserving keys, 8 bits a pass, two launches a pass; nothing is sorted or stored. */
+int mi_snake_order_stats(const mi_array *image, int64_t k0, int64_t k1, void *work_dev, mi_stream stream);
+/* out (int8) = src > 0 (nonzero = 0) or src != 0 (nonzero = 1); src: C-contiguous, any dtype but float16. */
+int mi_snake_binarize(const mi_array *src, const mi_array *out, int nonzero, mi_stream stream);
+/* out = 1 / sqrt(1 + T(alpha) gradnorm) in T, every operation rounded on its own (inverse_gaussian_gradient, morphsnakes.py:266) */
+int mi_snake_inverse_gradient(const mi_array *gradnorm, const mi_array *out, double alpha, mi_stream stream);
+
 /* ------------------------------------------------------------------ */
 /* K5: interpolation, spline order 0 and 1                              */
 /* ------------------------------------------------------------------ */
