@@ -35,8 +35,7 @@ SOURCES = [
     ("separable3d.hip", []),
     ("stream3d.hip", []),
     ("stream_f64.hip", []),
-    # MI_LONG_TUNE=1 in the environment adds the tuning variants of the 17-tap kernel (mi_debug_set_long_cfg)
-    ("sep3d_long.hip", ["-DMI_LONG_TUNE"] if os.environ.get("MI_LONG_TUNE") else []),
+    ("sep3d_long.hip", []),
     ("minmax3d_f32.hip", []),
     ("correlate_nd.hip", ["-ffp-contract=off"]),
     ("stencil3d.hip", ["-ffp-contract=off"]),
@@ -149,7 +148,7 @@ def _compile(args):
     stamp_file = o + ".flags"
     stamp = _flag_stamp(flags)
     try:
-        same_flags = open(stamp_file).read() == stamp       # e.g. MI_LONG_TUNE toggled: rebuild
+        same_flags = open(stamp_file).read() == stamp       # flags changed: rebuild
     except OSError:
         same_flags = False
     if (not force and same_flags and os.path.exists(o) and os.path.getmtime(o) >= os.path.getmtime(s)
@@ -190,7 +189,6 @@ def _compile(args):
 
 # Sources whose kernels wait on vmcnt by count (LDS-DMA rings): the name fragment selects the kernels that must not
 # touch scratch memory (a spill store or reload is one more vector-memory operation in flight than the count assumes).
-# The ablation builds of the r3 long kernel (<W, SAME, DBG = true, 0>) are exempt: timing aids, not product kernels.
 NO_SCRATCH = {"sep3d_long.hip": "sep3d_long", "minmax3d_f32.hip": "mm3f32_long", "interp_fast.hip": ("zstream_kernel", "zrect_kernel"), "interp.hip": "cubic3_zstream_kernel", "cubic_fast.hip": "cubic3_zfactor_kernel"}
 
 
@@ -250,18 +248,6 @@ def _device_code_object(obj):
     raise RuntimeError("no {} code object in {}".format(ARCH, obj))
 
 
-def _is_ablation_build(mangled):
-    """sep3d_long3_kernel<W, SAME, DBG = true, ...>: the ablation builds (timing aids behind a debug knob, not product
-    kernels) may spill.  Decided from the template arguments of the Itanium-mangled name -- `Lb1E` in third position --
-    not from one exact suffix, so that a new trailing parameter or a renamed parameter struct cannot silently turn the
-    exemption off (or on for a product kernel)."""
-    m = re.search(r"sep3d_long[34]_kernelI((?:L[a-z]n?\d+E)+)E", mangled)
-    if not m:
-        return False
-    targs = re.findall(r"L([a-z])(n?\d+)E", m.group(1))
-    return len(targs) >= 3 and targs[2] == ("b", "1")
-
-
 def _scratch_users(obj, fragment):
     """Kernels of `obj` whose name contains `fragment` and whose code has scratch_* instructions."""
     import tempfile
@@ -274,7 +260,7 @@ def _scratch_users(obj, fragment):
     bad, name, count = [], None, 0
     def close():
         frags = fragment if isinstance(fragment, tuple) else (fragment,)
-        if name and count and any(f in name for f in frags) and not _is_ablation_build(name):
+        if name and count and any(f in name for f in frags):
             bad.append("{} ({} scratch / compiler-made AGPR instructions)".format(name, count))
     for line in text.splitlines():
         m = re.match(r"^[0-9a-f]+ <(\S+)>:$", line)

@@ -63,6 +63,8 @@ mm3f32_long_kernel(const float *__restrict__ in, float *__restrict__ out, const 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
+    // tile decode, DMA source offsets and plane issue: a copy of the prologue of sep3d_long3_kernel (sep3d_long.hip; the
+    // differences are listed there: one plane range, no zero fill, no `xsrc >= 0` test, `nt` hint at every size)
     int b = blockIdx.x;
     const int total = p.nxt * p.nyt * p.nzc;
     if ((total & 7) == 0) b = (b & 7) * (total >> 3) + (b >> 3);

@@ -55,8 +55,6 @@ struct LongParams {
     // wxo[2k+1] = wx[2k] (pairs starting at an odd tap; wxo[0] = 0)
     float wyp[kStreamMaxTaps + 1], wzp[kStreamMaxTaps + 1], wxe[kStreamMaxTaps + 1], wxo[kStreamMaxTaps + 1];
     int nt;                 // 1 = rows no other workgroup reads are staged non-temporally (long_common.hpp, stream_nt_for)
-    int dbg;                // tuning ablations (0 in production): 1 y pass reads one row, 2 no x pass, 4 no z scatter, 8 no DMA, 16 no stores, 32 no halo table,
-                            // 64 halo table at the end of the step (r3 kernel), 128 nothing (selects the ablation build)
 };
 
 // SAME: the three axes share one weight vector (uniform_filter(size=W), isotropic gaussian_filter): x pair tables
@@ -122,6 +120,8 @@ sep3d_long_kernel(const float *__restrict__ in, float *__restrict__ out, const L
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
+    // tile decode, DMA source offsets and plane issue: the r3 and r4 kernels below and mm3f32_long_kernel (minmax3d_f32.hip)
+    // hold copies of this prologue; what differs between them is listed at sep3d_long3_kernel
     int b = blockIdx.x;
     const int total = p.nxt * p.nyt * p.nzc;
     if ((total & 7) == 0) b = (b & 7) * (total >> 3) + (b >> 3);
@@ -227,7 +227,7 @@ sep3d_long_kernel(const float *__restrict__ in, float *__restrict__ out, const L
         rin.y = (unsigned)(a >> 32);       // stride 0: the upper 16 bits of a device address are zero
         rin.z = live ? plane_bytes : 0u;
         rin.w = 0x00020000u;
-        if (!(p.dbg & 8)) dma_two_rows(rin, vmain[0], vhalo[0], vmain[1], vhalo[1], bufoff + (unsigned)wave * kLongRec);
+        dma_two_rows(rin, vmain[0], vhalo[0], vmain[1], vhalo[1], bufoff + (unsigned)wave * kLongRec);
     };
     constexpr int kArgBase = 2 * sizeof(void *);
     kfloats wyk = kernarg_floats(kArgBase + offsetof(LongParams, wyv));
@@ -239,7 +239,6 @@ sep3d_long_kernel(const float *__restrict__ in, float *__restrict__ out, const L
     auto ypass = [&](unsigned at) {
         const float4 t0 = *reinterpret_cast<const float4 *>(smem + at);
         F4 yv = f4_scale2((f32x2){wyk[0], wyk[1]}, f4_from(t0));
-        if (p.dbg & 1) return yv;
 #pragma unroll
         for (int k = 1; k < W; k++) {
             const float4 t = *reinterpret_cast<const float4 *>(smem + at + k * kLongRec);
@@ -277,10 +276,8 @@ sep3d_long_kernel(const float *__restrict__ in, float *__restrict__ out, const L
                 // Oldest first, this wave has in flight: the 4 DMAs of plane i + 1 (issued two steps ago), the store of
                 // step i - 2, the 4 DMAs of plane i + 2 and the store of step i - 1 (vector memory operations of a wave
                 // retire in issue order on gfx9).  Plane i + 1 must have landed; plane i + 2 AND the store behind it stay
-                // in flight: vmcnt(5) once stores have begun.  (r2 waited vmcnt(4) throughout, i.e. for the first DMA of
-                // the plane issued one step earlier: a prefetch distance of one plane, not two -- removing the DMAs
-                // altogether saved 86 us of 358 on config B, the waves were stalling on them.)
-                if (i >= W && !(p.dbg & 16)) asm volatile(MI_VMCNT(5) " lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                // in flight: vmcnt(5) once stores have begun, vmcnt(4) before.
+                if (i >= W) asm volatile(MI_VMCNT(5) " lgkmcnt(0)\n\ts_barrier" ::: "memory");
                 else asm volatile(MI_VMCNT(4) " lgkmcnt(0)\n\ts_barrier" ::: "memory");
                 issue(i + 3, b3);
                 const unsigned hyoff = (unsigned)(i & 1) * (kLongHyBytes / 2);
@@ -292,14 +289,12 @@ sep3d_long_kernel(const float *__restrict__ in, float *__restrict__ out, const L
                     const float4 f = *reinterpret_cast<const float4 *>(smem + hy_far + hyoff);
                     eL[0] = n; eL[1] = f; eR[0] = n; eR[1] = f;
                 }
-                const F4 xy = (p.dbg & 2) ? yv : xhops<W>(f4_to_float4(yv), eL, eR, lane, last, xt0, xt1);
+                const F4 xy = xhops<W>(f4_to_float4(yv), eL, eR, lane, last, xt0, xt1);
                 // ---- z pass: scatter into the pending outputs; output i - k takes tap k
                 acc[J] = f4_scale2((f32x2){wzk[0], wzk[1]}, xy);
-                if (!(p.dbg & 4)) {
 #pragma unroll
-                    for (int k = 1; k < W; k++)
-                        acc[(J - k + W) % W] = f4_fma2((f32x2){wzk[2 * k], wzk[2 * k + 1]}, xy, acc[(J - k + W) % W]);
-                }
+                for (int k = 1; k < W; k++)
+                    acc[(J - k + W) % W] = f4_fma2((f32x2){wzk[2 * k], wzk[2 * k + 1]}, xy, acc[(J - k + W) % W]);
                 if (i >= W - 1) {
                     const unsigned long long oa = (unsigned long long)out +
                                                   (unsigned long long)(unsigned)(zs + i - (W - 1)) * (unsigned long long)plane_bytes;
@@ -312,10 +307,10 @@ sep3d_long_kernel(const float *__restrict__ in, float *__restrict__ out, const L
                         o.lo = fma2(splat2(g1), oxv.lo, o.lo + splat2(g0));
                         o.hi = fma2(splat2(g1), oxv.hi, o.hi + splat2(g0));
                     }
-                    if (!(p.dbg & 16)) __builtin_amdgcn_raw_buffer_store_b128(f4_to_u32(o), rout, ovoff, 0, 2);
+                    __builtin_amdgcn_raw_buffer_store_b128(f4_to_u32(o), rout, ovoff, 0, 2);
                 }
                 // ---- halo table of plane i + 1 (the wave changes every plane)
-                if (i + 1 < nsteps && wave == (i & 15) && !(p.dbg & 32)) {
+                if (i + 1 < nsteps && wave == (i & 15)) {
                     const F4 hv = ypass(hsrc + b1);
                     *reinterpret_cast<float4 *>(smem + HY0 + (kLongHyBytes / 2 - hyoff) + (unsigned)lane * 16u) = f4_to_float4(hv);
                 }
@@ -326,244 +321,6 @@ sep3d_long_kernel(const float *__restrict__ in, float *__restrict__ out, const L
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-
-#ifdef MI_LONG_TUNE
-// ---------------------------------------------------------------------------
-// r3 (tuning builds, MI_LONG_TUNE): the r2 stream with TWO output rows per wave (8 waves, 256 x 16 tile, same LDS ring and DMA scheme).
-// The y pass of rows j and j + 1 reads W + 1 raw rows instead of 2 W (the 17-tap kernel is bound by VALU issue and by
-// the LDS reads the y pass waits for: rocprofv3 showed the VALU 61 % busy and ~600 k cycles per CU for ~365 k cycles of
-// VALU work; ablations in DESIGN.md): 9.5 instead of 17 ds_read_b128 per output row, twice the independent FMA work
-// behind every LDS wait, two waves per SIMD (up to 256 VGPRs: the 2 x W z accumulators take 136).
-// ---------------------------------------------------------------------------
-template <int W, bool SAME, bool HAS_CONST>
-__global__ void __launch_bounds__(512)
-sep3d_long2_kernel(const float *__restrict__ in, float *__restrict__ out, const LongParams p)
-{
-    constexpr int NW = 8;                       // waves; wave w owns output rows 2 w, 2 w + 1
-    constexpr int ROWS = kLongTY + W - 1;
-    static_assert(W >= 3 && (W & 1) && ROWS <= kLongRowsMax && W / 2 <= 8, "long kernel: odd W, 3..17");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr unsigned HY0 = kLongRawBytes;
-    int *ztab = reinterpret_cast<int *>(smem + kLongRawBytes + kLongHyBytes);
-    float *cztab = reinterpret_cast<float *>(ztab + kLongMaxChunk + kStreamMaxTaps);
-    float *oztab = cztab + kLongMaxChunk;
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-
-    int b = blockIdx.x;
-    const int total = p.nxt * p.nyt * p.nzc;
-    if ((total & 7) == 0) b = (b & 7) * (total >> 3) + (b >> 3);
-    const int per_chunk = p.nxt * p.nyt;
-    const int zci = b / per_chunk;
-    const int rem = b - zci * per_chunk;
-    const int yt = rem / p.nxt, xt = rem - yt * p.nxt;
-
-    const int nx = p.nx, ny = p.ny, nz = p.nz;
-    const int x0 = xt * p.tw, y0 = yt * kLongTY;
-    int zs, ze;
-    {
-        const bool second = zci >= p.nzc0;
-        const int zb = second ? p.zb1 : p.zb0, zn = second ? p.zn1 : p.zn0;
-        zs = zb + (second ? zci - p.nzc0 : zci) * p.zc;
-        ze = min(zs + p.zc, zb + zn);
-    }
-    const int ty_act = min(kLongTY, ny - y0);
-    const int rows_needed = ty_act + W - 1;
-    const int nlanes = min(p.tw >> 2, (nx - x0) >> 2);
-    const int last = nlanes - 1;
-    const int xe = x0 + 4 * nlanes;
-    const unsigned plane_bytes = (unsigned)ny * (unsigned)nx * 4u;
-    const int zi0 = zs - p.oz;
-    const int nsteps = ze - zs + W - 1;
-
-    for (int i = threadIdx.x; i < nsteps; i += NW * 64) ztab[i] = bmap<int>(zi0 + i, nz, p.mz);
-    [[maybe_unused]] float cyv[2] = {0.f, 0.f}, oyv[2] = {0.f, 0.f};
-    [[maybe_unused]] F4 oxv = f4_splat(0.f);
-    if constexpr (HAS_CONST) {
-        for (int t = threadIdx.x; t < ze - zs; t += NW * 64) {
-            float c = 0.f, o = 0.f;
-            for (int k = 0; k < W; k++) {
-                const int q = zs + t - p.oz + k;
-                const bool in = p.mz != MI_MODE_CONSTANT || (q >= 0 && q < nz);
-                c += in ? p.wzv[2 * k] : 0.f;
-                o += in ? 0.f : p.wzv[2 * k];
-            }
-            cztab[t] = c;
-            oztab[t] = o;
-        }
-        float ox4[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int k = 0; k < W; k++) {
-#pragma unroll
-            for (int r = 0; r < 2; r++) {
-                const int qy = y0 + 2 * wave + r - p.oy + k;
-                const bool iny = p.my != MI_MODE_CONSTANT || (qy >= 0 && qy < ny);
-                cyv[r] += iny ? p.wyv[2 * k] : 0.f;
-                oyv[r] += iny ? 0.f : p.wyv[2 * k];
-            }
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                const int qx = x0 + 4 * lane + c - W / 2 + k;
-                ox4[c] += (p.mx != MI_MODE_CONSTANT || (qx >= 0 && qx < nx)) ? 0.f : p.wxs[k];
-            }
-        }
-        oxv.lo = (f32x2){ox4[0], ox4[1]};
-        oxv.hi = (f32x2){ox4[2], ox4[3]};
-    }
-    __syncthreads();
-
-    // raw rows this wave stages per plane: wave, wave + 8, wave + 16, wave + 24
-    unsigned vmain[4], vhalo[4];
-#pragma unroll
-    for (int h = 0; h < 4; h++) {
-        const int r = wave + NW * h;
-        const int ys = bmap<int>(y0 - p.oy + r, ny, p.my);
-        const bool valid = r < rows_needed && ys >= 0;
-        vmain[h] = (valid && lane < nlanes) ? (unsigned)(ys * nx + x0 + 4 * lane) * 4u : kOOB;
-        const int j = lane & 15;
-        const int xsrc = bmap<int>(j < 8 ? x0 - 8 + j : xe + j - 8, nx, p.mx);
-        vhalo[h] = (valid && xsrc >= 0) ? (unsigned)(ys * nx + xsrc) * 4u : kOOB;
-    }
-    const unsigned own = (unsigned)(2 * wave) * kLongRec + (unsigned)lane * 16u;    // first raw record of output row 2 w
-    const unsigned hsrc = (unsigned)(lane >> 2) * kLongRec + 1024u + (unsigned)(lane & 3) * 16u;
-    unsigned hy_near[2], hy_far[2], ovoff[2];
-#pragma unroll
-    for (int r = 0; r < 2; r++) {
-        const int j = 2 * wave + r;
-        hy_near[r] = HY0 + (unsigned)j * 64u + (lane == 0 ? 16u : 32u);
-        hy_far[r] = HY0 + (unsigned)j * 64u + (lane == 0 ? 0u : 48u);
-        ovoff[r] = (j < ty_act && lane < nlanes) ? (unsigned)((y0 + j) * nx + x0 + 4 * lane) * 4u : kOOB;
-    }
-    constexpr unsigned kPlane = kLongRowsMax * kLongRec;
-
-    auto issue = [&](int i, unsigned bufoff) {
-        bool live = i < nsteps;
-        int zsrc = zi0 + i;
-        if ((unsigned)zsrc >= (unsigned)nz) zsrc = __builtin_amdgcn_readfirstlane(ztab[live ? i : 0]);
-        if constexpr (HAS_CONST) {
-            live = live && zsrc >= 0;
-            zsrc = max(zsrc, 0);
-        }
-        const unsigned long long a = (unsigned long long)in + (unsigned long long)(unsigned)zsrc * (unsigned long long)plane_bytes;
-        u32x4_t rin;
-        rin.x = (unsigned)a;
-        rin.y = (unsigned)(a >> 32);
-        rin.z = live ? plane_bytes : 0u;
-        rin.w = 0x00020000u;
-        if (!(p.dbg & 8)) {
-            dma_two_rows(rin, vmain[0], vhalo[0], vmain[2], vhalo[2], bufoff + (unsigned)wave * kLongRec);            // rows w, w + 16
-            dma_two_rows(rin, vmain[1], vhalo[1], vmain[3], vhalo[3], bufoff + (unsigned)(wave + NW) * kLongRec);     // rows w + 8, w + 24
-        }
-    };
-    constexpr int kArgBase = 2 * sizeof(void *);
-    kfloats wyk = kernarg_floats(kArgBase + offsetof(LongParams, wyv));
-    kfloats wzk = SAME ? wyk : kernarg_floats(kArgBase + offsetof(LongParams, wzv));
-    kfloats xt0 = kernarg_floats(kArgBase + offsetof(LongParams, xpair));
-    kfloats xt1 = xt0 + 2 * (kStreamMaxTaps / 2 + 2);
-
-    // y pass of ONE row (the halo table): W consecutive records starting at LDS byte address `at`
-    auto ypass = [&](unsigned at) {
-        const float4 t0 = *reinterpret_cast<const float4 *>(smem + at);
-        F4 yv = f4_scale2((f32x2){wyk[0], wyk[1]}, f4_from(t0));
-#pragma unroll
-        for (int k = 1; k < W; k++) {
-            const float4 t = *reinterpret_cast<const float4 *>(smem + at + k * kLongRec);
-            yv = f4_fma2((f32x2){wyk[2 * k], wyk[2 * k + 1]}, f4_from(t), yv);
-        }
-        return yv;
-    };
-    // y pass of rows j and j + 1 from the W + 1 records starting at `at`: raw row k is tap k of row j, tap k - 1 of row j + 1
-    auto ypass2 = [&](unsigned at, F4 &ya, F4 &yb) {
-        const float4 t0 = *reinterpret_cast<const float4 *>(smem + at);
-        ya = f4_scale2((f32x2){wyk[0], wyk[1]}, f4_from(t0));
-        if (p.dbg & 1) { yb = ya; return; }
-#pragma unroll
-        for (int k = 1; k < W; k++) {
-            const F4 t = f4_from(*reinterpret_cast<const float4 *>(smem + at + k * kLongRec));
-            ya = f4_fma2((f32x2){wyk[2 * k], wyk[2 * k + 1]}, t, ya);
-            if (k == 1) yb = f4_scale2((f32x2){wyk[0], wyk[1]}, t);
-            else yb = f4_fma2((f32x2){wyk[2 * k - 2], wyk[2 * k - 1]}, t, yb);
-        }
-        const F4 t = f4_from(*reinterpret_cast<const float4 *>(smem + at + W * kLongRec));
-        yb = f4_fma2((f32x2){wyk[2 * W - 2], wyk[2 * W - 1]}, t, yb);
-    };
-
-    F4 acc[2][W];
-#pragma unroll
-    for (int r = 0; r < 2; r++)
-#pragma unroll
-        for (int k = 0; k < W; k++) acc[r][k] = f4_splat(0.f);
-
-    issue(0, 0);
-    issue(1, kPlane);
-    issue(2, 2 * kPlane);
-    asm volatile(MI_VMCNT(16) "\n\ts_barrier" ::: "memory");
-    if (wave == NW - 1) {
-        const F4 hv = ypass(hsrc);
-        *reinterpret_cast<float4 *>(smem + HY0 + (unsigned)lane * 16u) = f4_to_float4(hv);
-    }
-
-    unsigned bi = 0;
-    for (int i0 = 0; i0 < nsteps; i0 += W) {
-        static_for<W>([&](auto JJ) {
-            constexpr int J = decltype(JJ)::value;
-            const int i = i0 + J;
-            if (i < nsteps) {
-                if constexpr (!SAME) { launder(wyk); launder(wzk); launder(xt0); launder(xt1); }
-                const unsigned b1 = bi == (kLongNB - 1) * kPlane ? 0u : bi + kPlane;
-                const unsigned b3 = bi == 0u ? (kLongNB - 1) * kPlane : bi - kPlane;
-                // in flight, oldest first: 8 DMAs of plane i + 1, 2 stores, 8 DMAs of plane i + 2, 2 stores (see the
-                // one-row kernel): plane i + 1 must have landed, the rest stays in flight
-                if (i >= W && !(p.dbg & 16)) asm volatile(MI_VMCNT(10) " lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                else asm volatile(MI_VMCNT(8) " lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                issue(i + 3, b3);
-                const unsigned hyoff = (unsigned)(i & 1) * (kLongHyBytes / 2);
-                F4 yv[2];
-                ypass2(own + bi, yv[0], yv[1]);
-#pragma unroll
-                for (int r = 0; r < 2; r++) {
-                    float4 eL[2], eR[2];
-                    {
-                        const float4 n = *reinterpret_cast<const float4 *>(smem + hy_near[r] + hyoff);
-                        const float4 f = *reinterpret_cast<const float4 *>(smem + hy_far[r] + hyoff);
-                        eL[0] = n; eL[1] = f; eR[0] = n; eR[1] = f;
-                    }
-                    const F4 xy = (p.dbg & 2) ? yv[r] : xhops<W>(f4_to_float4(yv[r]), eL, eR, lane, last, xt0, xt1);
-                    acc[r][J] = f4_scale2((f32x2){wzk[0], wzk[1]}, xy);
-                    if (!(p.dbg & 4)) {
-#pragma unroll
-                        for (int k = 1; k < W; k++)
-                            acc[r][(J - k + W) % W] = f4_fma2((f32x2){wzk[2 * k], wzk[2 * k + 1]}, xy, acc[r][(J - k + W) % W]);
-                    }
-                }
-                if (i >= W - 1) {
-                    const unsigned long long oa = (unsigned long long)out +
-                                                  (unsigned long long)(unsigned)(zs + i - (W - 1)) * (unsigned long long)plane_bytes;
-                    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void *)oa, 0, (int)plane_bytes, 0x00020000);
-#pragma unroll
-                    for (int r = 0; r < 2; r++) {
-                        F4 o = acc[r][(J + 1) % W];
-                        if constexpr (HAS_CONST) {
-                            const float czv = cztab[i - (W - 1)];
-                            const float g1 = p.cval * czv * cyv[r];
-                            const float g0 = oztab[i - (W - 1)] * p.cval_sxy + czv * (p.cval_sx * oyv[r]);
-                            o.lo = fma2(splat2(g1), oxv.lo, o.lo + splat2(g0));
-                            o.hi = fma2(splat2(g1), oxv.hi, o.hi + splat2(g0));
-                        }
-                        if (!(p.dbg & 16)) __builtin_amdgcn_raw_buffer_store_b128(f4_to_u32(o), rout, ovoff[r], 0, 2);
-                    }
-                }
-                if (i + 1 < nsteps && wave == (i & (NW - 1)) && !(p.dbg & 32)) {
-                    const F4 hv = ypass(hsrc + b1);
-                    *reinterpret_cast<float4 *>(smem + HY0 + (kLongHyBytes / 2 - hyoff) + (unsigned)lane * 16u) = f4_to_float4(hv);
-                }
-                bi = b1;
-            }
-        });
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-#endif
 
 // ---------------------------------------------------------------------------
 // r3 kernel (`sep3d_long3_kernel`): same tile, ring, DMA and barrier scheme; what changed is the instruction stream,
@@ -581,7 +338,6 @@ sep3d_long2_kernel(const float *__restrict__ in, float *__restrict__ out, const 
 //   * The DPP lane shifts take the left halo blocks straight from their own LDS reads as the `old` operand (no
 //     v_mov per shifted register) and the right-hand shifts leave lane 63 undefined (the select for lane `last`
 //     follows anyway).
-//   * The ablation flags are a template parameter: the production instance is straight-line code.
 // Index-mapping boundary modes only: constant mode (zero fill + correction terms, five more live registers) stays on
 // sep3d_long_kernel, whose register budget has room for them.
 // ---------------------------------------------------------------------------
@@ -690,9 +446,6 @@ struct XPass3 {
     }
 };
 
-// CFG (tuning, see launch_long): bits 0-2 first y read group, bits 3-6 end of the second group, bit 7 halo table at
-// the end of the step instead of the start, bit 8 no priority raise for the wave that makes the halo table, bit 9 x pass through LDS; 0 = the
-// defaults below.
 // WZ: taps along z (the streamed axis); W: taps along y and x.  WZ != W serves volumes with anisotropic voxels
 // (gaussian sigma given in millimetres: fewer taps through the slices), where the in-plane kernels agree.
 // RG (r6): rows of any length >= 16 floats.  The LDS-DMA takes 16-byte records from addresses that are only 4-byte aligned
@@ -701,30 +454,27 @@ struct XPass3 {
 // floats are replaced by the first y-filtered halo floats right of the row -- the halo DMA starts at the row's true end -- and
 // the two right-hand halo blocks move up by 4 - tail floats; the lane stores `tail` floats (one 8-byte and one 4-byte store
 // that every lane issues with an out-of-range offset, so that the vmcnt arithmetic stays uniform: three stores per step).
-template <int W, bool SAME, bool DBG, int CFG = 0, int WZ = W, bool RG = false>
+template <int W, bool SAME, int WZ = W, bool RG = false>
 __global__ void __launch_bounds__(kLongTY * 64)
 sep3d_long3_kernel(const float *__restrict__ in, float *__restrict__ out, const LongParams p)
 {
-    static_assert(!RG || (CFG == 0 && !DBG), "the ragged build is the production variant only");
     constexpr int ROWS = kLongTY + W - 1;
     static_assert(W >= 3 && (W & 1) && ROWS <= kLongRowsMax && W / 2 <= 8, "long kernel: odd W, 3..17");
     static_assert(WZ >= 3 && (WZ & 1) && WZ <= kLongRowsMax / 2 + 1 && (WZ == W || !SAME), "long kernel: odd WZ, 3..17");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr unsigned HY0 = kLongRawBytes;
     int *ztab = reinterpret_cast<int *>(smem + kLongRawBytes + kLongHyBytes);
-    const int dbg = DBG ? p.dbg : 0;
-    // CFG bit 9: the x pass through LDS.  The pipelined y pass never reads plane i in step i, so three ring slots do; the
-    // fourth holds, twice (step parity), one record per wave: [8 halo floats][the wave's y-filtered row][8 halo floats].
-    // A wave stores its row, the wave that makes the halo table stores the halo blocks there, and the x window is five
-    // aligned 16-byte reads -- no lane shifts, no edge selects (24 + copies of the 136 VALU instructions per step).
-    constexpr bool kXlds = ((CFG >> 9) & 1) != 0;
-    constexpr int kSlots = kXlds ? 3 : kLongNB;
-    constexpr unsigned kXrow0 = 3u * kLongRowsMax * kLongRec;                   // byte offset of the x records (kXlds)
-    constexpr unsigned kXpar = (unsigned)kLongTY * kLongRec;                    // bytes per parity
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
+    // Tile decode, DMA source offsets and plane issue.  Four kernels hold a copy of this prologue (r2 above, this one, r4
+    // below, mm3f32_long_kernel in minmax3d_f32.hip); a change to the DMA recipe goes into all four.  They differ in: ragged
+    // rows (RG: here and min/max); zero fill of rows / planes that bmap() puts outside the array (`ys >= 0`, `zsrc >= 0`: here;
+    // r2 tests rows always and planes under HAS_CONST; r4 and min/max never run `constant` mode); the `xsrc >= 0` test (not in
+    // min/max); two output plane ranges (LongParams) or one (MmLongParams); the `nt` hint (here up to 9 taps, min/max always,
+    // r2 and r4 never); z taps in nsteps (WZ here and in r4, W elsewhere).  A shared __forceinline__ form was tried: hipcc
+    // compiled every instance of this kernel, of r4 and of min/max to different code on top of it (17 taps: with spills).
     int b = blockIdx.x;
     const int total = p.nxt * p.nyt * p.nzc;
     if ((total & 7) == 0) b = (b & 7) * (total >> 3) + (b >> 3);
@@ -774,11 +524,6 @@ sep3d_long3_kernel(const float *__restrict__ in, float *__restrict__ out, const 
     const unsigned hsrc = (unsigned)(lane >> 2) * kLongRec + 1024u + (unsigned)(lane & 3) * 16u;
     // this row's four y-filtered halo blocks in the table: far left, near left, near right, far right
     const unsigned hy_row = HY0 + (unsigned)wave * 64u;
-    // kXlds: where lane (row = lane / 4, block = lane % 4) of the halo pass stores: blocks 0, 1 in front of the row, blocks
-    // 2, 3 right behind its last valid float4
-    const unsigned hx_dst = kXrow0 + (unsigned)(lane >> 2) * kLongRec +
-                            ((lane & 3) < 2 ? (unsigned)(lane & 3) * 16u : 32u + 16u * (unsigned)nlanes + (unsigned)((lane & 3) - 2) * 16u);
-    const unsigned xr_own = kXrow0 + (unsigned)wave * kLongRec + (unsigned)lane * 16u;     // block -2 of this lane's window
     const bool rg_last = RG && lane == last && tail < 4;                     // stores `tail` floats in pieces
     const bool rg_p1 = rg_last && tail < 2, rg_p2 = rg_last && tail < 3, rg_p3 = rg_last;     // floats 1 / 2 / 3 of its block are the row's continuation
     const unsigned ovoff0 = (unsigned)((y0 + wave) * nx + x0 + 4 * lane) * 4u;
@@ -804,9 +549,9 @@ sep3d_long3_kernel(const float *__restrict__ in, float *__restrict__ out, const 
         // (up to 9 taps: the kernels that wait for memory; the longer ones are bound by what a wave issues, and the second
         // copy of the DMA statement cost the 17-tap kernel 6 %)
         if constexpr (W <= 9) {
-            if (!(dbg & 8)) dma_two_rows(rin, vmain[0], vhalo[0], vmain[1], vhalo[1], bufoff + (unsigned)wave * kLongRec, p.nt && wave >= W - 1);
+            dma_two_rows(rin, vmain[0], vhalo[0], vmain[1], vhalo[1], bufoff + (unsigned)wave * kLongRec, p.nt && wave >= W - 1);
         } else {
-            if (!(dbg & 8)) dma_two_rows(rin, vmain[0], vhalo[0], vmain[1], vhalo[1], bufoff + (unsigned)wave * kLongRec);
+            dma_two_rows(rin, vmain[0], vhalo[0], vmain[1], vhalo[1], bufoff + (unsigned)wave * kLongRec);
         }
     };
     constexpr int kArgBase = 2 * sizeof(void *);
@@ -819,7 +564,6 @@ sep3d_long3_kernel(const float *__restrict__ in, float *__restrict__ out, const 
     auto ypass = [&](unsigned at) {
         const float4 t0 = *reinterpret_cast<const float4 *>(smem + at);
         F4 yv = f4_scale(wyk[0], f4_from(t0));
-        if (dbg & 1) return yv;
 #pragma unroll
         for (int k = 1; k < W; k++) {
             const float4 t = *reinterpret_cast<const float4 *>(smem + at + k * kLongRec);
@@ -831,20 +575,19 @@ sep3d_long3_kernel(const float *__restrict__ in, float *__restrict__ out, const 
     // the same for the wave that makes the halo table on top of its own step: all reads in flight as early as the
     // registers allow (9, then 4 more as each 4 are consumed) -- what this pass costs the workgroup is its latency
     auto ypass_batched = [&](unsigned at) {
-        constexpr int H0 = DBG ? 5 : 9, H = W < H0 ? W : H0;
+        constexpr int H = W < 9 ? W : 9;
         float4 t[W];
-        const int rows = (dbg & 1) ? 1 : W;
         const char *src = smem + at;
 #pragma unroll
-        for (int k = 0; k < H; k++) if (k < rows) t[k] = *reinterpret_cast<const float4 *>(src + k * kLongRec);
+        for (int k = 0; k < H; k++) t[k] = *reinterpret_cast<const float4 *>(src + k * kLongRec);
         __builtin_amdgcn_sched_barrier(0);
         F4 hv = f4_scale(wyk[0], f4_from(t[0]));
         static_for<(W + 3) / 4>([&](auto GG) {
             constexpr int g = decltype(GG)::value;
 #pragma unroll
-            for (int k = 4 * g; k < 4 * g + 4 && k < W; k++) if (k >= 1 && k < rows) hv = f4_fma(wyk[k], f4_from(t[k]), hv);
+            for (int k = 4 * g; k < 4 * g + 4 && k < W; k++) if (k >= 1) hv = f4_fma(wyk[k], f4_from(t[k]), hv);
 #pragma unroll
-            for (int k = H + 4 * g; k < H + 4 * g + 4 && k < W; k++) if (k < rows) t[k] = *reinterpret_cast<const float4 *>(src + k * kLongRec);
+            for (int k = H + 4 * g; k < H + 4 * g + 4 && k < W; k++) t[k] = *reinterpret_cast<const float4 *>(src + k * kLongRec);
             __builtin_amdgcn_sched_barrier(0);
         });
         return hv;
@@ -862,8 +605,7 @@ sep3d_long3_kernel(const float *__restrict__ in, float *__restrict__ out, const 
     F4 yv = ypass(own);
     if (wave == 15) {
         const F4 hv = ypass(hsrc);
-        if constexpr (kXlds) *reinterpret_cast<float4 *>(smem + hx_dst) = f4_to_float4(hv);
-        else *reinterpret_cast<float4 *>(smem + HY0 + (unsigned)lane * 16u) = f4_to_float4(hv);
+        *reinterpret_cast<float4 *>(smem + HY0 + (unsigned)lane * 16u) = f4_to_float4(hv);
     }
 
     // Interval i (after barrier i): plane i + 1 has landed (each wave waited for its own DMAs of plane i + 1; those of
@@ -876,128 +618,98 @@ sep3d_long3_kernel(const float *__restrict__ in, float *__restrict__ out, const 
             const int i = i0 + J;
             if (i < nsteps) {
                 if constexpr (!SAME) { launder(wyk); launder(wzk); launder(xte); launder(xto); }
-                const unsigned b1 = bi == (kSlots - 1) * kPlane ? 0u : bi + kPlane;     // plane i + 1
-                // where plane i + 3 goes: the slot of plane i - 1 in the ring of four, of plane i in the ring of three
-                const unsigned b3 = kXlds ? bi : (bi == 0u ? (kLongNB - 1) * kPlane : bi - kPlane);
+                const unsigned b1 = bi == (kLongNB - 1) * kPlane ? 0u : bi + kPlane;     // plane i + 1
+                const unsigned b3 = bi == 0u ? (kLongNB - 1) * kPlane : bi - kPlane;     // slot of plane i - 1: where plane i + 3 goes
                 // In flight from this wave, oldest first: the 4 DMAs of plane i + 1, the store of step i - 2, the 4 DMAs
                 // of plane i + 2, the store of step i - 1 (a store is issued in EVERY step: before the first complete
                 // output it goes to a descriptor of zero records).  Plane i + 1 must have landed: vmcnt(5); step 0 has
                 // only the 8 DMAs of the prologue behind it: vmcnt(4).
-                if ((J == 0 && i0 == 0) || (dbg & 16)) asm volatile(MI_VMCNT(4) " lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                if (J == 0 && i0 == 0) asm volatile(MI_VMCNT(4) " lgkmcnt(0)\n\ts_barrier" ::: "memory");
                 else if constexpr (RG) asm volatile(MI_VMCNT(7) " lgkmcnt(0)\n\ts_barrier" ::: "memory");    // three stores per step
                 else asm volatile(MI_VMCNT(5) " lgkmcnt(0)\n\ts_barrier" ::: "memory");
                 const unsigned hyoff = (unsigned)(i & 1) * (kLongHyBytes / 2);
                 // ---- halo table of plane i + 1 (the wave changes every plane).  First thing in the step: its reads travel
                 // while the other waves of the SIMD have their whole step to issue.
-                auto halo_job = [&]() {
-                    if (i + 1 < nsteps && wave == (i & 15) && !(dbg & 32)) {
-                        // this wave has one row more to filter than the other three of its SIMD: it goes first for the rest
-                        // of the step, so that the extra work is shared out instead of left over at the barrier
-                        if constexpr (((CFG >> 8) & 1) == 0) __builtin_amdgcn_s_setprio(3);
-                        const F4 hv = ypass_batched(hsrc + b1);
-                        if constexpr (kXlds) *reinterpret_cast<float4 *>(smem + hx_dst + (unsigned)((i + 1) & 1) * kXpar) = f4_to_float4(hv);
-                        else *reinterpret_cast<float4 *>(smem + HY0 + (kLongHyBytes / 2 - hyoff) + (unsigned)lane * 16u) = f4_to_float4(hv);
-                    }
-                };
-                constexpr bool kHaloEnd = (CFG >> 7) & 1;
-                if (kHaloEnd ? (dbg & 64) != 0 : !(dbg & 64)) halo_job();
+                if (i + 1 < nsteps && wave == (i & 15)) {
+                    // this wave has one row more to filter than the other three of its SIMD: it goes first for the rest
+                    // of the step, so that the extra work is shared out instead of left over at the barrier
+                    __builtin_amdgcn_s_setprio(3);
+                    const F4 hv = ypass_batched(hsrc + b1);
+                    *reinterpret_cast<float4 *>(smem + HY0 + (kLongHyBytes / 2 - hyoff) + (unsigned)lane * 16u) = f4_to_float4(hv);
+                }
                 // ---- x and z passes of plane i, with the y pass of plane i + 1 (for the next step; past the last plane it
                 // reads a slot nobody needs) threaded through them by hand: the LDS reads of a group are issued one block
                 // of FMAs before they are consumed (sched_barrier keeps the compiler from regrouping them; the group
-                // sizes are what the register file allows: 128 VGPRs, 68 of them z accumulators).  
-#ifndef MI_LONG_GA
-#define MI_LONG_GA 4
-#endif
-                constexpr int GA0 = CFG ? (CFG & 7) : MI_LONG_GA;
-                constexpr int GB0 = CFG ? ((CFG >> 3) & 15) : DBG ? 8 : SAME ? 12 : 10;     // the re-loading variants keep more scalars alive, the ablation build its flags
-                constexpr int GA = W < GA0 ? W : GA0, GB = W < GB0 ? W : GB0, ZH = WZ / 2;
-                const int wy_rows = (dbg & 1) ? 1 : W, wz_taps = (dbg & 4) ? 1 : WZ;
+                // sizes are what the register file allows: 128 VGPRs, 68 of them z accumulators).
+                constexpr int GA = W < 4 ? W : 4, GB0 = SAME ? 12 : 10, GB = W < GB0 ? W : GB0, ZH = WZ / 2;     // the re-loading variants keep more scalars alive
                 float4 R[W];
                 const char *ysrc = smem + own + b1;
                 issue(i + 3, b3);
                 XPass3<W> xp;
                 float4 yv4 = f4_to_float4(yv);
                 F4 xy;
-                if constexpr (kXlds) {
-                    constexpr int NBK = XPass3<W>::NBK;
-                    float4 blk[2 * NBK + 1];
-                    char *xr = smem + xr_own + (unsigned)(i & 1) * kXpar;
-                    *reinterpret_cast<float4 *>(xr + 32) = yv4;                    // own block: behind the 8 halo floats
-                    // LDS operations of a wave are carried out in order: the reads below see the row
-#pragma unroll
-                    for (int b = 0; b < 2 * NBK + 1; b++)
-                        if (b != NBK) blk[b] = *reinterpret_cast<const float4 *>(xr + 32 + 16 * (b - NBK));
-                    blk[NBK] = yv4;
-#pragma unroll
-                    for (int k = 0; k < GA; k++) if (k < wy_rows) R[k] = *reinterpret_cast<const float4 *>(ysrc + k * kLongRec);
-                    __builtin_amdgcn_sched_barrier(0);
-                    xy = (dbg & 2) ? yv : xp.window(blk, xte, xto);
-                    __builtin_amdgcn_sched_barrier(0);
-                } else {
-                    float4 oL[2], eR[2];
-                    oL[1] = *reinterpret_cast<const float4 *>(smem + hy_row + hyoff);
-                    oL[0] = *reinterpret_cast<const float4 *>(smem + hy_row + hyoff + 16u);
-                    if constexpr (RG) {
-                        // the row's continuation h0 .. h7 (the y-filtered halo floats from the row's true end: blocks 2, 3 of the
-                        // table row) moves into the last lane's block behind its `tail` floats, and the two right-hand blocks
-                        // start 4 - tail floats later: twelve consecutive floats of the table row from float 8 - tail on (dword
-                        // reads: the address is only 4-byte aligned; past h7 they are another row's, wanted by no stored output)
-                        const float *hp = reinterpret_cast<const float *>(smem + hy_row + hyoff + 32u - 4u * (unsigned)tail);
-                        const float u1 = hp[1], u2 = hp[2], u3 = hp[3];
-                        eR[0] = make_float4(hp[4], hp[5], hp[6], hp[7]);
-                        eR[1] = make_float4(hp[8], hp[9], hp[10], hp[11]);
-                        yv4.y = rg_p1 ? u1 : yv4.y;
-                        yv4.z = rg_p2 ? u2 : yv4.z;
-                        yv4.w = rg_p3 ? u3 : yv4.w;
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (!(dbg & 2)) xp.left(yv4, oL, xte, xto);
-                    if constexpr (!RG) {
-                        eR[0] = *reinterpret_cast<const float4 *>(smem + hy_row + hyoff + 32u);
-                        eR[1] = *reinterpret_cast<const float4 *>(smem + hy_row + hyoff + 48u);
-                    }
-#pragma unroll
-                    for (int k = 0; k < GA; k++) if (k < wy_rows) R[k] = *reinterpret_cast<const float4 *>(ysrc + k * kLongRec);
-                    __builtin_amdgcn_sched_barrier(0);
-                    xy = (dbg & 2) ? yv : xp.right(yv4, eR, lane, last, xte, xto);
-                    __builtin_amdgcn_sched_barrier(0);
+                float4 oL[2], eR[2];
+                oL[1] = *reinterpret_cast<const float4 *>(smem + hy_row + hyoff);
+                oL[0] = *reinterpret_cast<const float4 *>(smem + hy_row + hyoff + 16u);
+                if constexpr (RG) {
+                    // the row's continuation h0 .. h7 (the y-filtered halo floats from the row's true end: blocks 2, 3 of the
+                    // table row) moves into the last lane's block behind its `tail` floats, and the two right-hand blocks
+                    // start 4 - tail floats later: twelve consecutive floats of the table row from float 8 - tail on (dword
+                    // reads: the address is only 4-byte aligned; past h7 they are another row's, wanted by no stored output)
+                    const float *hp = reinterpret_cast<const float *>(smem + hy_row + hyoff + 32u - 4u * (unsigned)tail);
+                    const float u1 = hp[1], u2 = hp[2], u3 = hp[3];
+                    eR[0] = make_float4(hp[4], hp[5], hp[6], hp[7]);
+                    eR[1] = make_float4(hp[8], hp[9], hp[10], hp[11]);
+                    yv4.y = rg_p1 ? u1 : yv4.y;
+                    yv4.z = rg_p2 ? u2 : yv4.z;
+                    yv4.w = rg_p3 ? u3 : yv4.w;
                 }
+                __builtin_amdgcn_sched_barrier(0);
+                xp.left(yv4, oL, xte, xto);
+                if constexpr (!RG) {
+                    eR[0] = *reinterpret_cast<const float4 *>(smem + hy_row + hyoff + 32u);
+                    eR[1] = *reinterpret_cast<const float4 *>(smem + hy_row + hyoff + 48u);
+                }
+#pragma unroll
+                for (int k = 0; k < GA; k++) R[k] = *reinterpret_cast<const float4 *>(ysrc + k * kLongRec);
+                __builtin_amdgcn_sched_barrier(0);
+                xy = xp.right(yv4, eR, lane, last, xte, xto);
+                __builtin_amdgcn_sched_barrier(0);
                 yv = f4_scale(wyk[0], f4_from(R[0]));
 #pragma unroll
-                for (int k = 1; k < GA; k++) if (k < wy_rows) yv = f4_fma(wyk[k], f4_from(R[k]), yv);
+                for (int k = 1; k < GA; k++) yv = f4_fma(wyk[k], f4_from(R[k]), yv);
 #pragma unroll
-                for (int k = GA; k < GB; k++) if (k < wy_rows) R[k] = *reinterpret_cast<const float4 *>(ysrc + k * kLongRec);
+                for (int k = GA; k < GB; k++) R[k] = *reinterpret_cast<const float4 *>(ysrc + k * kLongRec);
                 __builtin_amdgcn_sched_barrier(0);
                 // z pass: scatter into the pending outputs; output i - k takes tap k
                 acc[J] = f4_scale(wzk[0], xy);
 #pragma unroll
-                for (int k = 1; k < ZH; k++) if (k < wz_taps) acc[(J - k + WZ) % WZ] = f4_fma(wzk[k], xy, acc[(J - k + WZ) % WZ]);
+                for (int k = 1; k < ZH; k++) acc[(J - k + WZ) % WZ] = f4_fma(wzk[k], xy, acc[(J - k + WZ) % WZ]);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int k = GA; k < GB; k++) if (k < wy_rows) yv = f4_fma(wyk[k], f4_from(R[k]), yv);
+                for (int k = GA; k < GB; k++) yv = f4_fma(wyk[k], f4_from(R[k]), yv);
 #pragma unroll
-                for (int k = GB; k < W; k++) if (k < wy_rows) R[k] = *reinterpret_cast<const float4 *>(ysrc + k * kLongRec);
+                for (int k = GB; k < W; k++) R[k] = *reinterpret_cast<const float4 *>(ysrc + k * kLongRec);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int k = ZH < 1 ? 1 : ZH; k < WZ; k++) if (k < wz_taps) acc[(J - k + WZ) % WZ] = f4_fma(wzk[k], xy, acc[(J - k + WZ) % WZ]);
+                for (int k = ZH < 1 ? 1 : ZH; k < WZ; k++) acc[(J - k + WZ) % WZ] = f4_fma(wzk[k], xy, acc[(J - k + WZ) % WZ]);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int k = GB; k < W; k++) if (k < wy_rows) yv = f4_fma(wyk[k], f4_from(R[k]), yv);
+                for (int k = GB; k < W; k++) yv = f4_fma(wyk[k], f4_from(R[k]), yv);
                 {
                     const unsigned long long oa = (unsigned long long)out +
                                                   (unsigned long long)(unsigned)(zs + i - (WZ - 1)) * (unsigned long long)plane_bytes;
                     const __amdgpu_buffer_rsrc_t rout =
                         __builtin_amdgcn_make_buffer_rsrc((void *)oa, 0, i >= WZ - 1 ? (int)plane_bytes : 0, 0x00020000);
                     const F4 o = acc[(J + 1) % WZ];
-                    if (!(dbg & 16)) __builtin_amdgcn_raw_buffer_store_b128(f4_to_u32(o), rout, ovoff, 0, 2);
+                    __builtin_amdgcn_raw_buffer_store_b128(f4_to_u32(o), rout, ovoff, 0, 2);
                     if constexpr (RG) {
                         const u32x4 ou = f4_to_u32(o);
                         __builtin_amdgcn_raw_buffer_store_b64((u32x2){ou.x, ou.y}, rout, ovoff2, 0, 2);
                         __builtin_amdgcn_raw_buffer_store_b32((tail & 2) ? ou.z : ou.x, rout, ovoff1, 0, 2);
                     }
                 }
-                if (kHaloEnd ? !(dbg & 64) : (dbg & 64) != 0) halo_job();
-                if constexpr (((CFG >> 8) & 1) == 0) __builtin_amdgcn_s_setprio(0);
+                __builtin_amdgcn_s_setprio(0);
                 bi = b1;
             }
         });
@@ -1023,12 +735,11 @@ sep3d_long3_kernel(const float *__restrict__ in, float *__restrict__ out, const 
 // Same tile, DMA statement, barrier and vmcnt scheme as the r3 kernel; index-mapping boundary modes; W with ROWS % 4 == 0.
 // ---------------------------------------------------------------------------
 typedef float f32x4m __attribute__((ext_vector_type(4)));
-template <int W, bool SAME, bool DBG = false, int WZ = W>
+template <int W, bool SAME, int WZ = W>
 __global__ void __launch_bounds__(kLongTY * 64)
 sep3d_long4_kernel(const float *__restrict__ in, float *__restrict__ out, const LongParams p)
 {
     constexpr int ROWS = kLongTY + W - 1, KS = ROWS / 4;
-    const int dbg = DBG ? p.dbg : 0;         // ablations (timing aids): 1 no y pass, 2 no x pass, 4 no z scatter, 8 no DMA, 16 no stores
     static_assert(W >= 5 && (W & 1) && ROWS <= kLongRowsMax && ROWS % 4 == 0, "long4 kernel: W = 5, 9, 13, 17");
     static_assert(WZ >= 3 && (WZ & 1) && WZ <= 17 && (WZ == W || !SAME), "long4 kernel: odd WZ");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1040,6 +751,7 @@ sep3d_long4_kernel(const float *__restrict__ in, float *__restrict__ out, const 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
+    // tile decode, DMA source offsets and plane issue: a copy of the prologue of sep3d_long3_kernel (differences listed there)
     int b = blockIdx.x;
     const int total = p.nxt * p.nyt * p.nzc;
     if ((total & 7) == 0) b = (b & 7) * (total >> 3) + (b >> 3);
@@ -1091,7 +803,7 @@ sep3d_long4_kernel(const float *__restrict__ in, float *__restrict__ out, const 
         rin.y = (unsigned)(a >> 32);
         rin.z = live ? plane_bytes : 0u;
         rin.w = 0x00020000u;
-        if (!(dbg & 8)) dma_two_rows(rin, vmain[0], vhalo[0], vmain[1], vhalo[1], bufoff + (unsigned)wave * kLongRec);
+        dma_two_rows(rin, vmain[0], vhalo[0], vmain[1], vhalo[1], bufoff + (unsigned)wave * kLongRec);
     };
     constexpr int kArgBase = 2 * sizeof(void *);
     kfloats wyk = kernarg_floats(kArgBase + offsetof(LongParams, wyp));
@@ -1172,7 +884,7 @@ sep3d_long4_kernel(const float *__restrict__ in, float *__restrict__ out, const 
     // the barrier), nobody reads Y(i - 1) or raw plane i any more: the slot of plane i takes plane i + 3, Y(i + 1) goes
     // where Y(i - 1) was.
     const unsigned xr_own = kY0 + (unsigned)wave * kLongRec + (unsigned)lane * 16u;       // block -2 of this lane's window in Y(i)
-    const bool vector_first = ((wave >> 2) & 1) != 0 && !(dbg & 64);
+    const bool vector_first = ((wave >> 2) & 1) != 0;
     unsigned bi = 0;                    // LDS offset of raw plane i
     for (int i0 = 0; i0 < nsteps; i0 += WZ) {
         static_for<WZ>([&](auto JJ) {
@@ -1197,22 +909,21 @@ sep3d_long4_kernel(const float *__restrict__ in, float *__restrict__ out, const 
 #pragma unroll
                     for (int q = 0; q < 2 * NBK + 1; q++) blk[q] = *reinterpret_cast<const float4 *>(xr + 32 + 16 * (q - NBK));
                     XPass3<W> xp;
-                    const F4 xy = (dbg & 2) ? f4_from(blk[NBK]) : xp.window(blk, xte, xto);
+                    const F4 xy = xp.window(blk, xte, xto);
                     // z pass: scatter into the pending outputs; output i - k takes tap k
                     acc[J] = f4_scale(wzk[0], xy);
-                    const int wz_taps = (dbg & 4) ? 1 : WZ;
 #pragma unroll
-                    for (int k = 1; k < WZ; k++) if (k < wz_taps) acc[(J - k + WZ) % WZ] = f4_fma(wzk[k], xy, acc[(J - k + WZ) % WZ]);
+                    for (int k = 1; k < WZ; k++) acc[(J - k + WZ) % WZ] = f4_fma(wzk[k], xy, acc[(J - k + WZ) % WZ]);
                     const unsigned long long oa = (unsigned long long)out +
                                                   (unsigned long long)(unsigned)(zs + i - (WZ - 1)) * (unsigned long long)plane_bytes;
                     const __amdgpu_buffer_rsrc_t rout =
                         __builtin_amdgcn_make_buffer_rsrc((void *)oa, 0, i >= WZ - 1 ? (int)plane_bytes : 0, 0x00020000);
                     const F4 o = acc[(J + 1) % WZ];
-                    if (!(dbg & 16)) __builtin_amdgcn_raw_buffer_store_b128(f4_to_u32(o), rout, ovoff, 0, 2);
+                    __builtin_amdgcn_raw_buffer_store_b128(f4_to_u32(o), rout, ovoff, 0, 2);
                 };
                 if (vector_first) xz();
                 __builtin_amdgcn_sched_barrier(0);
-                if (i + 1 < nsteps && !(dbg & 1)) yplane(i + 1, b1);
+                if (i + 1 < nsteps) yplane(i + 1, b1);
                 __builtin_amdgcn_sched_barrier(0);
                 if (!vector_first) xz();
                 bi = b1;
@@ -1222,16 +933,8 @@ sep3d_long4_kernel(const float *__restrict__ in, float *__restrict__ out, const 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-static mi::Knob g_long_rows{0};        // kernel generation: 0 / 3 = the r3 pipelined kernel, 1 = the r2 kernel (kept for 9 / 13 / 17 taps as the comparator), 4 = the r4 kernel with the y pass on the matrix cores (9 / 13 / 17 taps; an experiment that did not pay)
-static mi::Knob g_long_dbg{0};         // tuning ablations, see LongParams::dbg
+static mi::Knob g_long_rows{0};        // kernel generation: 0 = the r3 pipelined kernel, 1 = the r2 kernel (kept for 9 / 13 / 17 taps as the comparator), 4 = the r4 kernel with the y pass on the matrix cores (9 / 13 / 17 taps; an experiment that did not pay)
 static mi::Knob g_long_const0{1};     // r5: 1 = constant mode with cval == 0 takes the r3 kernel (zero fill by the staging), 0 = the r2 kernel with its correction
-static mi::Knob g_long_cfg{0};         // MI_LONG_TUNE builds: which tuning variant of the 17-tap kernel runs
-
-#ifdef MI_LONG_DEV
-#define MI_LONG_OLD(W) ((W) == 17)
-#else
-#define MI_LONG_OLD(W) ((W) == 9 || (W) == 13 || (W) == 17)
-#endif
 
 template <typename K>
 static int long_launch_one(K kernel, PerDeviceOnce &attr_done, size_t lds, int total, const float *in, float *out, const LongParams &p, hipStream_t s)
@@ -1258,72 +961,39 @@ static int launch_long(const float *in, float *out, LongParams &p, hipStream_t s
             static PerDeviceOnce attr_z;
             note_kernel("mi::sep3d_long3_kernel<%d,%s> grid=%d (fused y/x/z separable pass, LDS-DMA staged, y pass one plane ahead; constant mode, zero fill)",
                         W, SAME ? "true" : "false", total);
-            return long_launch_one(sep3d_long3_kernel<W, SAME, false>, attr_z, lds, total, in, out, p, s);
+            return long_launch_one(sep3d_long3_kernel<W, SAME>, attr_z, lds, total, in, out, p, s);
         }
         // any other fill value keeps the r2 kernel: its correction terms (five more live registers) do not fit beside the r3
         // kernel's read groups without spilling, and a spill is a vector-memory operation the vmcnt arithmetic does not count
-        static PerDeviceOnce attr_c;
-        note_kernel("mi::sep3d_long_kernel<%d,%s,true> grid=%d (fused y/x/z separable pass, LDS-DMA staged, constant mode)", W,
-                    SAME ? "true" : "false", total);
-        return long_launch_one(sep3d_long_kernel<W, SAME, true>, attr_c, lds, total, in, out, p, s);
+        // (from 9 taps: run_sep3d_long leaves shorter kernels with a fill value to the streaming passes)
+        if constexpr (W >= 9) {
+            static PerDeviceOnce attr_c;
+            note_kernel("mi::sep3d_long_kernel<%d,%s,true> grid=%d (fused y/x/z separable pass, LDS-DMA staged, constant mode)", W,
+                        SAME ? "true" : "false", total);
+            return long_launch_one(sep3d_long_kernel<W, SAME, true>, attr_c, lds, total, in, out, p, s);
+        } else {
+            return MI_ERR_UNSUPPORTED;
+        }
     } else {
-        if constexpr (MI_LONG_OLD(W)) {
+        if constexpr (W == 9 || W == 13 || W == 17) {
             if (g_long_rows == 1) {
                 static PerDeviceOnce attr_old;
                 note_kernel("mi::sep3d_long_kernel<%d,%s,false> grid=%d (fused y/x/z separable pass, LDS-DMA staged, r2 instruction stream)", W,
                             SAME ? "true" : "false", total);
                 return long_launch_one(sep3d_long_kernel<W, SAME, false>, attr_old, lds, total, in, out, p, s);
             }
-            // the ablation flags exist in these instances only
-            if (p.dbg != 0 && g_long_rows != 4) {
-                static PerDeviceOnce attr_dbg;
-                note_kernel("mi::sep3d_long3_kernel<%d,%s,true> grid=%d (ablation build, dbg=%d)", W, SAME ? "true" : "false", total, p.dbg);
-                return long_launch_one(sep3d_long3_kernel<W, SAME, true>, attr_dbg, lds, total, in, out, p, s);
-            }
-        }
-#ifdef MI_LONG_TUNE
-        if constexpr (W == 17 && SAME) {
-            if (g_long_rows == 2) {
-                static PerDeviceOnce attr2;
-                if (!attr2) {
-                    MI_HIP(hipFuncSetAttribute((const void *)sep3d_long2_kernel<17, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    attr2 = true;
-                }
-                note_kernel("mi::sep3d_long2_kernel<17,true,false> grid=%d (r2 stream, two rows per wave; tuning build)", total);
-                hipLaunchKernelGGL((sep3d_long2_kernel<17, true, false>), dim3(total), dim3(512), lds, s, in, out, p);
-                MI_HIP(hipGetLastError());
-                return MI_OK;
-            }
-            const int cfg = g_long_cfg;
-#define MI_LONG_CFG(C)                                                                                           \
-            if (cfg == (C)) {                                                                                    \
-                static PerDeviceOnce attr_c;                                                                      \
-                note_kernel("mi::sep3d_long3_kernel<17,true,false,%d> grid=%d (tuning variant)", (C), total);    \
-                return long_launch_one(sep3d_long3_kernel<17, true, false, (C)>, attr_c, lds, total, in, out, p, s); \
-            }
-            MI_LONG_CFG(4 | (12 << 3) | 512) MI_LONG_CFG(4 | (10 << 3) | 512) MI_LONG_CFG(4 | (8 << 3) | 512)
-#undef MI_LONG_CFG
-        }
-#endif
-        if constexpr (W == 9 || W == 13 || W == 17) {
             if (g_long_rows == 4) {                 // not the default: 268 against 261 us on config B (fp32 MFMAs and the packed FMAs share one datapath)
                 static PerDeviceOnce attr4;
                 const size_t lds4 = 3 * (size_t)kLongRowsMax * kLongRec + 2 * (size_t)kLongTY * kLongRec + (size_t)(kLongMaxChunk + kStreamMaxTaps) * sizeof(int);
                 note_kernel("mi::sep3d_long4_kernel<%d,%s> grid=%d (fused y/x/z separable pass, LDS-DMA staged, y pass on the matrix cores)", W,
                             SAME ? "true" : "false", total);
-                if constexpr (W == 17 && SAME) {
-                    if (p.dbg != 0) {
-                        static PerDeviceOnce attr4d;
-                        return long_launch_one(sep3d_long4_kernel<W, SAME, true>, attr4d, lds4, total, in, out, p, s);
-                    }
-                }
                 return long_launch_one(sep3d_long4_kernel<W, SAME>, attr4, lds4, total, in, out, p, s);
             }
         }
         static PerDeviceOnce attr_done;
         note_kernel("mi::sep3d_long3_kernel<%d,%s> grid=%d (fused y/x/z separable pass, LDS-DMA staged, y pass one plane ahead)", W,
                     SAME ? "true" : "false", total);
-        return long_launch_one(sep3d_long3_kernel<W, SAME, false>, attr_done, lds, total, in, out, p, s);
+        return long_launch_one(sep3d_long3_kernel<W, SAME>, attr_done, lds, total, in, out, p, s);
     }
 }
 
@@ -1332,15 +1002,11 @@ static int long_cus() { return device_cus(); }
 // (in-plane taps, z taps) pairs the r3 kernel is instantiated for besides the cubic ones (r4: with more z taps too): volumes with anisotropic
 // voxels, where a gaussian given in millimetres has fewer taps through the slices (each pair is one more kernel to
 // compile: the list is what sigma = 0.5 ... 2 voxels in the plane, in steps of a quarter, needs with 2-4 x thicker slices)
-#ifdef MI_LONG_DEV
-#define MI_LONG_ANISO_PAIRS(X) X(17, 9)
-#else
 #define MI_LONG_ANISO_PAIRS(X)                                                                             \
     X(5, 3) X(7, 3) X(7, 5) X(9, 3) X(9, 5) X(9, 7) X(11, 3) X(11, 5) X(11, 7) X(13, 3) X(13, 5) X(13, 7) X(13, 9)     \
     X(15, 5) X(15, 7) X(15, 9) X(17, 3) X(17, 5) X(17, 7) X(17, 9) X(17, 13)                                           \
     /* r4: MORE taps along z than in the plane (sigma larger through the slices: gaussian (2, 1, 1) = 17 x 9 x 9) */     \
     X(5, 9) X(5, 13) X(5, 17) X(7, 13) X(9, 13) X(9, 17) X(13, 17)
-#endif
 bool long_aniso_pair(int w, int wzn)
 {
 #define MI_LONG_ANISO_TEST(N, NZ) if (w == (N) && wzn == (NZ)) return true;
@@ -1388,7 +1054,6 @@ int run_sep3d_long(const float *in, float *out, int nz, int ny, int nx, int w, i
         p.wzv[2 * k] = p.wzv[2 * k + 1] = wz[k];
         p.wzp[k] = wz[k];
     }
-    p.dbg = g_long_dbg;
     p.nt = stream_nt_for((long long)nz * ny * nx * 8, p.nxt);
     p.cval = cval;
     p.cval_sx = (float)((double)cval * sx);
@@ -1431,7 +1096,7 @@ int run_sep3d_long(const float *in, float *out, int nz, int ny, int nx, int w, i
             static PerDeviceOnce attr_a;                                                                              \
             note_kernel("mi::sep3d_long3_kernel<%d,false,false,0,%d> grid=%d (fused y/x/z separable pass, %d taps in the plane, %d along z)", \
                         (N), (NZ), p.nxt * p.nyt * p.nzc, (N), (NZ));                                                 \
-            return long_launch_one(sep3d_long3_kernel<(N), false, false, 0, (NZ)>, attr_a, lds, p.nxt * p.nyt * p.nzc, in, out, p, s); \
+            return long_launch_one(sep3d_long3_kernel<(N), false, (NZ)>, attr_a, lds, p.nxt * p.nyt * p.nzc, in, out, p, s); \
         }
         MI_LONG_ANISO_PAIRS(MI_LONG_ANISO)
 #undef MI_LONG_ANISO
@@ -1449,7 +1114,7 @@ int run_sep3d_long(const float *in, float *out, int nz, int ny, int nx, int w, i
         case N: {                                                                                                         \
             static PerDeviceOnce attr_r;                                                                                  \
             note_kernel("mi::sep3d_long3_kernel<%d,true,ragged> grid=%d (fused y/x/z separable pass, LDS-DMA staged, rows of any length)", (N), total); \
-            return long_launch_one(sep3d_long3_kernel<(N), true, false, 0, (N), true>, attr_r, lds, total, in, out, p, s); \
+            return long_launch_one(sep3d_long3_kernel<(N), true, (N), true>, attr_r, lds, total, in, out, p, s); \
         }
         switch (w) {
             MI_LONG_RAGGED(9) MI_LONG_RAGGED(11) MI_LONG_RAGGED(13) MI_LONG_RAGGED(15) MI_LONG_RAGGED(17)
@@ -1464,11 +1129,7 @@ int run_sep3d_long(const float *in, float *out, int nz, int ny, int nx, int w, i
         if (has_const) return same ? launch_long<N, true, true>(in, out, p, s) : launch_long<N, false, true>(in, out, p, s); \
         return same ? launch_long<N, true, false>(in, out, p, s) : launch_long<N, false, false>(in, out, p, s);
     switch (w) {
-#ifdef MI_LONG_DEV
-        MI_LONG_CASE(17)
-#else
         MI_LONG_CASE(3) MI_LONG_CASE(5) MI_LONG_CASE(7) MI_LONG_CASE(9) MI_LONG_CASE(11) MI_LONG_CASE(13) MI_LONG_CASE(15) MI_LONG_CASE(17)
-#endif
     }
 #undef MI_LONG_CASE
     return MI_ERR_UNSUPPORTED;
@@ -1479,7 +1140,5 @@ int run_sep3d_long(const float *in, float *out, int nz, int ny, int nx, int w, i
 extern "C" int mi_debug_set_stream_nt(int k) { mi::g_stream_nt = k; return MI_OK; }
 extern "C" int mi_debug_set_long_zchunks(int n) { mi::g_long_zchunks = n; return MI_OK; }
 extern "C" int mi_debug_set_long_same(int n) { mi::g_long_same = n; return MI_OK; }
-extern "C" int mi_debug_set_long_dbg(int f) { mi::g_long_dbg = f; return MI_OK; }
 extern "C" int mi_debug_set_long_rows(int k) { mi::g_long_rows = k; return MI_OK; }
-extern "C" int mi_debug_set_long_cfg(int k) { mi::g_long_cfg = k; return MI_OK; }
 extern "C" int mi_debug_set_long_const0(int k) { mi::g_long_const0 = k; return MI_OK; }
