@@ -150,6 +150,12 @@ SIGNATURES = {
     "mi_snake_order_stats": [_arr, ctypes.c_int64, ctypes.c_int64, _vp, _vp],
     "mi_snake_binarize": [_arr, _arr, _i, _vp],
     "mi_snake_inverse_gradient": [_arr, _arr, _d, _vp],
+    "mi_tvl1_coords": [_arr, _arr, _vp],
+    "mi_tvl1_prepare": [_arr, _arr, _arr, _arr, _arr, _arr, _vp],
+    "mi_tvl1_data": [_arr, _arr, _arr, _arr, _d, _vp],
+    "mi_tvl1_scratch_size": [_arr, _i64p],
+    "mi_tvl1_reg": [_arr, _arr, _arr, _arr, _vp, _d, _d, _ip, _vp],
+    "mi_tvl1_diff_sum": [_arr, _arr, _vp, _vp],
     "mi_map_coordinates": [_arr, _arr, _arr, _i, _i, _d, _vp],
     "mi_affine_transform": [_arr, _arr, _dp, _i, _i, _d, _vp],
     "mi_spline_pad": [_arr, _arr, _i, _i, _d, _vp],

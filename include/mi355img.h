@@ -661,6 +661,45 @@ int mi_snake_binarize(const mi_array *src, const mi_array *out, int nonzero, mi_
 /* out = 1 / sqrt(1 + T(alpha) gradnorm) in T, every operation rounded on its own (inverse_gaussian_gradient, morphsnakes.py:266) */
 int mi_snake_inverse_gradient(const mi_array *gradnorm, const mi_array *out, double alpha, mi_stream stream);
 
+/* The TV-L1 optical flow solver (skimage.registration.optical_flow_tvl1; cupyimg/skimage/registration/_optical_flow.py:20-158,
+ * which runs a fixed-point iteration as about 140 whole-array operations; csrc/tvl1.hip).  The images are C-contiguous float32 /
+ * float64 arrays (T) of rank nd = 2 .. 4 with at least 2 samples along every axis (numpy.gradient's rule; other dtypes:
+ * MI_ERR_UNSUPPORTED with nothing queued); flow, grad and coords have shape (nd, *shape), proj (nd, nd, *shape), all of dtype T
+ * and C-contiguous.  All arithmetic in T, every product and sum rounded on its own, sums over the component axis left to right;
+ * a fixed number of iterations gives the bits of a NumPy transcription of the reference.  Nothing synchronises.
+ *
+ * mi_tvl1_coords: coords_a(q) = T(q_a) + flow_a(q), the sampling points of the warp.
+ * mi_tvl1_prepare (once per warp; w = the warped moving image):
+ *     grad_a = numpy.gradient(w) along axis a: (w(q + e_a) - w(q - e_a)) / 2 inside, one-sided differences at the two ends
+ *     NI     = (grad_0 grad_0 + grad_1 grad_1) + ..., 1 where that is 0
+ *     rho_0  = (w - reference) - ((grad_0 flow_0 + grad_1 flow_1) + ...)
+ * mi_tvl1_data (the data term, in place on `flow`, which then is the reference's flow_auxiliary):
+ *     rho = rho_0 + ((grad_0 flow_0 + grad_1 flow_1) + ...)
+ *     where |rho| <= T(f0) NI: flow_a -= (rho grad_a) / NI;  elsewhere: flow_a -= (T(f0) sign(rho)) grad_a
+ * mi_tvl1_reg (the regularisation), for every flow component c with v = flow_aux[c], p^0 = proj_in[c], u^0 = v, for s = 1, 2:
+ *     g_a    = u^(s-1)(q + e_a) - u^(s-1)(q) where q_a < n_a - 1, else 0
+ *     norm   = sqrt((g_0 g_0 + g_1 g_1) + ...) * T(f1) + 1;   p^s_a = (p^(s-1)_a - T(dt) g_a) / norm
+ *     d      = -((p^s_0(q) + p^s_1(q)) + ...), then for a = 0, 1, ...: d += p^s_a(q - e_a) where q_a >= 1;   u^s = v + d
+ *   flow_out[c] = u^2, proj_out[c] = p^2.  flow_out is not flow_aux and proj_out is not proj_in (no workgroup reads what another
+ *   writes in the same launch); the caller zeroes proj once per pyramid level and swaps the buffers between calls.  Rank 2 and
+ *   3: one launch (tvl1_reg_fused_kernel: a workgroup stages one component of a tile of flow_aux with a halo of 2 voxels either
+ *   way, and of proj_in with 2 voxels towards smaller and 1 towards larger indices, in LDS, streams along axis 0 and runs both
+ *   steps in one tile residency).  Other ranks, or after mi_debug_set_tvl1(.., 1): four launches with one thread per voxel
+ *   straight from global memory, p^1 and u^1 in scratch_dev, which then holds mi_tvl1_scratch_size elements of T (0 on the
+ *   fused route, where scratch_dev may be NULL).  *launches (may be NULL) receives the number of launches queued.
+ * mi_tvl1_diff_sum: sum (a - b)^2 over two arrays of one shape, the difference and its square in T, the sum in double from
+ *   per-workgroup partials in an order fixed by the size (no floating-point atomics); work_dev: MI_TVL1_WORK_BYTES of device
+ *   memory, the sum is the double at its start once the two launches have run. */
+#define MI_TVL1_WORK_BYTES 16384
+int mi_tvl1_coords(const mi_array *flow, const mi_array *coords, mi_stream stream);
+int mi_tvl1_prepare(const mi_array *warped, const mi_array *reference, const mi_array *flow, const mi_array *grad,
+                    const mi_array *ni, const mi_array *rho0, mi_stream stream);
+int mi_tvl1_data(const mi_array *grad, const mi_array *ni, const mi_array *rho0, const mi_array *flow, double f0, mi_stream stream);
+int mi_tvl1_scratch_size(const mi_array *flow, int64_t *elements);
+int mi_tvl1_reg(const mi_array *flow_aux, const mi_array *proj_in, const mi_array *flow_out, const mi_array *proj_out,
+                void *scratch_dev, double dt, double f1, int *launches, mi_stream stream);
+int mi_tvl1_diff_sum(const mi_array *a, const mi_array *b, void *work_dev, mi_stream stream);
+
 /* ------------------------------------------------------------------ */
 /* K5: interpolation, spline order 0 and 1                              */
 /* ------------------------------------------------------------------ */

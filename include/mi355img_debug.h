@@ -98,7 +98,8 @@ int mi_debug_set_tv_chambolle(int tile_rows, int chunk_planes, int narrow_tiles,
 int mi_debug_set_clahe(int force_generic, int force_shared_hist);   /* csrc/exposure.hip: force_generic = 1: mi_clahe_apply takes clahe_generic_kernel (one thread per voxel) for ranks 2 and 3 too; force_shared_hist = 1: mi_clahe_maps keeps one shared histogram per workgroup whatever the number of bins */
 int mi_debug_set_ridges(int tile_rows, int tile_planes, int force_generic);   /* csrc/ridges.hip: rows and planes of ridge_tile_kernel's tiles (0 = the planner's choice; a forced tile is also 16 columns wide instead of 64, so that small arrays have seams along every axis); force_generic = 1: every call takes hessian_generic_kernel and eig_generic_kernel (the Hessian elements in memory, one thread per voxel) */
 int mi_debug_set_morphsnakes(int small_boxes, int force_generic);   /* csrc/morphsnakes.hip: small_boxes = 1: snake_fused_kernel works on core boxes of 3 x 3 x 5 voxels (3 x 5 pixels) instead of the planner's, so that small arrays have seams along every axis; force_generic = 1: every stage of every call takes snake_generic_kernel (one stage per launch, one thread per voxel) */
-int mi_debug_morphsnakes_launches(void);      /* csrc/morphsnakes.hip: kernel launches queued by the mi_snake_* entry points since the library was loaded (a count, not a status) */
+int mi_debug_set_tvl1(int small_tiles, int force_generic);   /* csrc/tvl1.hip: small_tiles = 1: tvl1_reg_fused_kernel works on tiles of 3 x 8 voxels in chunks of 3 planes instead of the planner's, so that small arrays have seams along every axis; force_generic = 1: every mi_tvl1_reg call takes the per-voxel kernels (four launches, u^1 and p^1 in the scratch block) */
+int mi_debug_morphsnakes_launches(void);     /* csrc/morphsnakes.hip: kernel launches queued by the mi_snake_* entry points since the library was loaded (a count, not a status) */
 
 #ifdef __cplusplus
 }
