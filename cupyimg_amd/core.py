@@ -223,7 +223,7 @@ class ndarray:
         return out
 
     def set(self, arr):
-        arr = np.ascontiguousarray(arr, dtype=self.dtype)
+        arr = np.ascontiguousarray(arr, dtype=self.dtype).reshape(np.shape(arr))     # (ascontiguousarray makes 0-d one-dimensional)
         if arr.shape != self.shape:
             raise ValueError("shape mismatch")
         self._touch()
@@ -260,6 +260,14 @@ class ndarray:
 
     def fill(self, value):
         self._touch()
+        if self.dtype == np.float16 or (self.dtype.kind in "iu" and self.dtype.itemsize == 8 and _is_wide_integer(value)):
+            # mi_fill takes the value as a double: 64-bit integers beyond 2**53 would come out rounded (and 2**63 - 1
+            # overflow the cast), and float16 is not a type it computes in.  The value is converted on the host, as NumPy
+            # converts it, and copied from one device element to every element (a source with zero strides).
+            one = ndarray((1,), self.dtype)
+            one.set(np.asarray(value, dtype=self.dtype).reshape(1))
+            _copy(one._view(self.shape, (0,) * self.ndim, one.ptr), self)
+            return
         d = self._desc()
         _lib.check(_lib.load().mi_fill(ctypes.byref(d), float(value), None))
 
@@ -344,8 +352,8 @@ class ndarray:
         else:
             src = asarray(np.asarray(value))
         if src.shape != dst.shape:
-            # allow leading unit-axis broadcasting of equal sizes only
-            if src.size == dst.size:
+            # shapes that agree once unit axes are dropped; nothing else (a (6, 4) source is not a (4, 6) one)
+            if [s for s in src.shape if s != 1] == [s for s in dst.shape if s != 1]:
                 src = src.reshape(dst.shape)
             else:
                 raise ValueError("could not broadcast input array from shape {} into shape {}".format(
@@ -353,8 +361,22 @@ class ndarray:
         _copy(src, dst)
 
 
+def _is_wide_integer(value):
+    """an integer value a double does not hold exactly"""
+    if isinstance(value, np.ndarray):
+        value = value[()] if value.ndim == 0 else None
+    return isinstance(value, (int, np.integer)) and not isinstance(value, (bool, np.bool_)) and abs(int(value)) > 2 ** 53
+
+
 def _copy(src, dst, round_half_even=False):
     dst._touch()
+    if src._mem is dst._mem or not (isinstance(src._mem, _Memory) and isinstance(dst._mem, _Memory)):
+        # possibly one allocation (views of one array, or foreign memory whose owner is unknown): NumPy assigns as if
+        # from a copy, the kernels read while they write (`a[1:] = a[:-1]` would be a race)
+        if src.ptr == dst.ptr and src.shape == dst.shape and src.strides == dst.strides and src.dtype == dst.dtype:
+            return                                  # the same view: nothing to do
+        if shares_memory(src, dst):
+            src = src.copy()
     a, b = src._desc(), dst._desc()
     _lib.check(_lib.load().mi_copy(ctypes.byref(a), ctypes.byref(b), int(round_half_even), None))
 
@@ -563,7 +585,8 @@ def free_all_blocks():
 
 def arrays_differ(a, b):
     """True when two device arrays of equal dtype / shape differ anywhere
-    (device-side comparison, one int32 read back)."""
+    (device-side comparison, one int32 read back).  The comparison is of bytes, not of values: NaNs with equal bits are
+    equal, +0.0 and -0.0 differ."""
     if a.shape != b.shape or a.dtype != b.dtype:
         raise ValueError("arrays_differ needs equal shapes and dtypes")
     a, b = ascontiguousarray(a), ascontiguousarray(b)

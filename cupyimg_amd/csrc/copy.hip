@@ -5,6 +5,7 @@
 // cupyimg/scipy/ndimage/_filters_core.py:94,107,154, morphology.py:313,321).
 // Cast rules follow _filters_core.py:166-187 / SciPy: truncate toward zero,
 // negative -> unsigned wraps.
+#include <cmath>
 #include <vector>
 
 #include "common.hpp"
@@ -144,7 +145,7 @@ __global__ void __launch_bounds__(256) elementwise_kernel(const T *__restrict__ 
 }
 
 // out = a * s + t (op 0) or clip(a, lo, hi) keeping entries equal to `keep`
-// when keep_flag is set (op 1); floating-point arrays (skimage facade: dtype
+// when keep_flag is set (op 1); NaN stays NaN and -0.0 stays -0.0, like np.clip; floating-point arrays (skimage facade: dtype
 // range scaling, warp's output clipping, _warps.py:745-787)
 template <typename T, typename TO = T>
 __global__ void __launch_bounds__(256) scalar_op_kernel(const T *__restrict__ a, TO *__restrict__ out, int64_t n, int op,
@@ -154,7 +155,7 @@ __global__ void __launch_bounds__(256) scalar_op_kernel(const T *__restrict__ a,
         const double x = (double)a[i];
         double r;
         if (op == 0) r = x * p0 + p1;
-        else r = (keep_flag && x == keep) ? x : fmin(fmax(x, p0), p1);
+        else r = (keep_flag && x == keep) ? x : (x < p0 ? p0 : (x > p1 ? p1 : x));    // comparisons, not fmin / fmax: those drop a NaN
         out[i] = (TO)r;
     }
 }
@@ -318,7 +319,7 @@ int mi_fill(const mi_array *dst, double value, mi_stream stream)
     const int64_t total = numel(dst);
     if (total == 0) return MI_OK;
     hipStream_t s = resolve_stream(stream);
-    if (value == 0.0 && is_contiguous(dst)) {
+    if (value == 0.0 && !std::signbit(value) && is_contiguous(dst)) {       // -0.0 is not all-zero bytes in a float array
         MI_HIP(hipMemsetAsync(dst->data, 0, (size_t)total * dtype_size(dst->dtype), s));
         return MI_OK;
     }

@@ -292,7 +292,7 @@ def scale_shift(a, scale, shift, dtype=None):
 
 
 def clip(a, lo, hi, keep=None):
-    """clip a float device array to [lo, hi]; entries equal to `keep` stay"""
+    """clip a float device array to [lo, hi]; entries equal to `keep` stay, and so does NaN (like np.clip)"""
     a = core.ascontiguousarray(a)
     out = core.empty(a.shape, a.dtype)
     da, dd = a._desc(), out._desc()
@@ -302,11 +302,15 @@ def clip(a, lo, hi, keep=None):
 
 
 def min_max(a):
-    """(min, max) of a device array as Python floats (one small read-back)"""
+    """(min, max) of a device array as Python floats (one small read-back).  NaNs are skipped (np.nanmin / np.nanmax);
+    an array of nothing but NaNs has no sample to report and gives (NaN, NaN), as np.min / np.max do.  64-bit integers
+    beyond 2**53 come back rounded to double."""
     a = core.ascontiguousarray(a)
     lo, hi = ctypes.c_double(), ctypes.c_double()
     da = a._desc()
     check(lib().mi_min_max(ctypes.byref(da), ctypes.byref(lo), ctypes.byref(hi), None))
+    if lo.value > hi.value:          # the reduction's start values (+inf, -inf) came back: every sample was a NaN
+        return float("nan"), float("nan")
     return lo.value, hi.value
 
 
