@@ -1284,12 +1284,16 @@ static bool cubic3_grid(const mi_array *out, InterpGeom *g, dim3 *grid)
 // spline coefficients: padded float64 copy + in-place prefilter
 // ---------------------------------------------------------------------------
 // out (float64, shape = in.shape + 2 npad on the real axes) = in extended by edge
-// replication (pad_mode 0) or by cval (pad_mode 1); rank padded to 3
+// replication (pad_mode 0) or by cval (pad_mode 1); rank padded to 3.
+// SciPy pads the image in ITS dtype (np.pad before the prefilter), so the ring holds cval cast to T -- -1000.3 is -1000
+// in an int16 image and float32(-1000.3) in a float32 one -- and only then converted to the coefficient type; the
+// taps beyond the ring read the caller's cval as it is (the gather kernels).
 template <typename T, typename CF, int ND = 3>
 __global__ void __launch_bounds__(256)
 spline_pad_kernel(const T *__restrict__ in, CF *__restrict__ out, InterpGeom g, int64_t nout, int npad, int pad_mode,
                   double cval)
 {
+    const double ring = (double)cast_from_f64<T>(cval);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nout; i += (int64_t)gridDim.x * blockDim.x) {
         int64_t r = i, pos = 0;
         bool outside = false;
@@ -1304,7 +1308,7 @@ spline_pad_kernel(const T *__restrict__ in, CF *__restrict__ out, InterpGeom g, 
             }
             pos += o * g.stride[d];
         }
-        out[i] = (CF)((outside && pad_mode == 1) ? cval : (double)in[pos]);
+        out[i] = (CF)((outside && pad_mode == 1) ? ring : (double)in[pos]);
     }
 }
 

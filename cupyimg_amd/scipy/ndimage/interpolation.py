@@ -65,7 +65,9 @@ _SPLINE_SAMPLES_AXIS0 = 0x100   # order bit 8 + d: axis d of the coefficient arr
 def _to_coefficients(input, order, mode, cval, prefilter, f32=False, exact=False, skip_axis=None):
     """(device array of B-spline coefficients, npad) for orders 2-5: float64, or float32
     on the float32 cubic route (the recursion itself always runs in double).
-    SciPy pads by 12 samples for `nearest` / `grid-constant` before filtering;
+    SciPy pads by 12 samples for `nearest` / `grid-constant` before filtering, and it pads the image itself: the
+    ring of `grid-constant` holds cval cast to the image's dtype (-1000.3 is -1000 in an int16 image, float32(-1000.3)
+    in a float32 one; mi_spline_pad casts it), while the taps beyond the ring read cval as given;
     prefilter=False interpolates the samples as if they were coefficients.
     `exact`: only prefilter kernels whose arithmetic is SciPy's operation for operation (no blocked recursion) --
     set when the result is rounded to an integer dtype, where the last bit of a coefficient decides exact .5 ties."""

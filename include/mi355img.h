@@ -719,7 +719,10 @@ int mi_affine_transform(const mi_array *in, const mi_array *out, const double *m
  * _spline_prefilter_core.py, _spline_kernel_weights.py, _interp_kernels.py:473-549).
  * The caller builds the float64 coefficient array -- mi_spline_pad (copy of any
  * real dtype, extended by npad samples per side on every axis: pad_mode 0 edge
- * replication, 1 cval; SciPy pads by 12 for `nearest` / `grid-constant`, else 0)
+ * replication, 1 cval; SciPy pads by 12 for `nearest` / `grid-constant`, else 0.
+ * The ring of pad_mode 1 holds cval CAST TO THE DTYPE OF `in` (C truncation for integers, != 0 for bool, rounded to
+ * float32 for float32), as SciPy pads the image itself before it filters: -1000.3 is -1000 in an int16 image.  The
+ * cval handed to mi_spline_map_coordinates / mi_spline_affine_transform, read beyond the ring, stays as given.)
  * followed by mi_spline_filter1d along every axis (spline_mode 0 mirror,
  * 1 reflect, 2 grid-wrap: reflect for reflect / nearest, grid-wrap for grid-wrap,
  * mirror otherwise) -- and interpolates it; coordinates refer to the unpadded
@@ -746,7 +749,8 @@ int mi_spline_pad(const mi_array *in, const mi_array *out, int npad, int pad_mod
 int mi_spline_filter1d(const mi_array *data, int axis, int order, int spline_mode, mi_stream stream);
 /* mi_spline_pad followed by mi_spline_filter1d along every axis longer than one sample, in one call
  * (the loop of spline_filter, interpolation.py:185-268); without padding and conversion the first
- * pass reads `in` directly instead of copying it first.
+ * pass reads `in` directly instead of copying it first.  pad_mode 1 fills the ring with cval cast to in's dtype
+ * (see mi_spline_pad above).
  * Precision of the streaming passes (orders 2 / 3 on volumes of >= 16384 lines: the default route; r5 advisor
  * finding): the causal sweep's running values stay in the COEFFICIENT type between the two sweeps -- rounded to
  * float32 on the float32 route -- and a line starts from a 20-term truncated sum; the one-thread-per-line kernels

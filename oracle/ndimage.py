@@ -548,16 +548,18 @@ def spline_filter(input, order=3, output=np.float64, mode="mirror"):
 
 
 def _spline_coefficients(input, order, mode, cval, prefilter):
-    """(float64 coefficients, npad): SciPy pads by 12 for nearest / grid-constant before prefiltering"""
-    x = _f64(input)
+    """(float64 coefficients, npad): SciPy pads by 12 for nearest / grid-constant before prefiltering.  It pads the
+    image itself, so the ring of grid-constant holds cval cast to the image's dtype (-1000.3 is -1000 in an int16 image,
+    float32(-1000.3) in a float32 one); the conversion to float64 comes after."""
+    x = np.asarray(input)
     npad = 0
     if order > 1 and prefilter:
         if mode == "nearest":
             npad, x = 12, np.pad(x, 12, mode="edge")
         elif mode == "grid-constant":
             npad, x = 12, np.pad(x, 12, mode="constant", constant_values=cval)
-        x = spline_filter(x, order, np.float64, mode)
-    return np.ascontiguousarray(x), npad
+        x = spline_filter(_f64(x), order, np.float64, mode)
+    return _f64(x), npad
 
 
 def map_coordinates(input, coordinates, output=None, order=1, mode="constant", cval=0.0,

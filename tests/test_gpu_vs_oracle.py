@@ -741,7 +741,8 @@ def test_spline_filter_matches_oracle(gpu, ndi, shape):
 def test_spline_interpolation_matches_oracle(gpu, ndi, shape, order):
     """map_coordinates / affine_transform / shift / zoom with spline orders 2-5:
     device coefficients (pad + prefilter) and tap loop against the oracle, which
-    restates SciPy 1.15.3 (agreement 1e-14 there)."""
+    restates SciPy 1.15.3 (agreement 1e-14 there).  The oracle is handed the float32 image the device gets: in
+    `grid-constant` SciPy pads the image in its own dtype, so the ring holds float32(0.7) there, not 0.7."""
     rng = np.random.default_rng(111)
     nd = len(shape)
     x = rng.standard_normal(shape).astype(np.float32)
@@ -754,22 +755,22 @@ def test_spline_interpolation_matches_oracle(gpu, ndi, shape, order):
     off = rng.standard_normal(nd) * 2
     for mode in SPLINE_MODES:
         for pf in (True, False):
-            ref = orc.map_coordinates(x.astype(np.float64), coords, order=order, mode=mode, cval=0.7, prefilter=pf)
+            ref = orc.map_coordinates(x, coords, order=order, mode=mode, cval=0.7, prefilter=pf, output=np.float64)
             got = ndi.map_coordinates(xd, cdev, order=order, mode=mode, cval=0.7, prefilter=pf, output=np.float64).get()
             assert _close(got, ref), ("map", mode, pf)
-        ref = orc.affine_transform(x.astype(np.float64), M, off, order=order, mode=mode, cval=0.7)
+        ref = orc.affine_transform(x, M, off, order=order, mode=mode, cval=0.7, output=np.float64)
         got = ndi.affine_transform(xd, M, off, order=order, mode=mode, cval=0.7, output=np.float64).get()
         assert _close(got, ref), ("affine", mode)
         # float32 in / out like a user would call it: same values rounded to float32
         got32 = ndi.affine_transform(xd, M, off, order=order, mode=mode, cval=0.7).get()
         assert got32.dtype == np.float32 and _close(got32, ref, 1e-6), ("affine f32", mode)
-        ref = orc.shift(x.astype(np.float64), 1.3, order=order, mode=mode, cval=0.7)
+        ref = orc.shift(x, 1.3, order=order, mode=mode, cval=0.7, output=np.float64)
         assert _close(ndi.shift(xd, 1.3, order=order, mode=mode, cval=0.7, output=np.float64).get(), ref), ("shift", mode)
         for gm in (False, True):
             import warnings
             with warnings.catch_warnings():
                 warnings.simplefilter("ignore")
-                ref = orc.zoom(x.astype(np.float64), 1.7, order=order, mode=mode, cval=0.7, grid_mode=gm)
+                ref = orc.zoom(x, 1.7, order=order, mode=mode, cval=0.7, grid_mode=gm, output=np.float64)
                 got = ndi.zoom(xd, 1.7, order=order, mode=mode, cval=0.7, grid_mode=gm, output=np.float64).get()
             assert got.shape == ref.shape and _close(got, ref), ("zoom", mode, gm)
 
