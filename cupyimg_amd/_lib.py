@@ -156,6 +156,13 @@ SIGNATURES = {
     "mi_tvl1_scratch_size": [_arr, _i64p],
     "mi_tvl1_reg": [_arr, _arr, _arr, _arr, _vp, _d, _d, _ip, _vp],
     "mi_tvl1_diff_sum": [_arr, _arr, _vp, _vp],
+    "mi_edge_filter": [_arr, _arr, _arr, _dp, _i, _i, _i, _d, _vp],
+    "mi_canny_nms": [_arr, _arr, _arr, _arr, _arr, _arr, _d, _d, _vp],
+    "mi_canny_threshold": [_arr, _arr, _arr, _arr, _d, _d, _vp],
+    "mi_masked_copy": [_arr, _arr, _arr, _vp],
+    "mi_canny_normalize": [_arr, _arr, _arr, _vp],
+    "mi_edge_pair_magnitude": [_arr, _arr, _arr, _d, _vp],
+    "mi_threshold_masks":[_arr, _arr, _arr, _d, _d, _arr, _arr, _vp],
     "mi_map_coordinates": [_arr, _arr, _arr, _i, _i, _d, _vp],
     "mi_affine_transform": [_arr, _arr, _dp, _i, _i, _d, _vp],
     "mi_spline_pad": [_arr, _arr, _i, _i, _d, _vp],

@@ -700,6 +700,59 @@ int mi_tvl1_reg(const mi_array *flow_aux, const mi_array *proj_in, const mi_arra
                 void *scratch_dev, double dt, double f1, int *launches, mi_stream stream);
 int mi_tvl1_diff_sum(const mi_array *a, const mi_array *b, void *work_dev, mi_stream stream);
 
+/* The n-D edge operators of skimage.filters -- sobel, scharr, prewitt, magnitude and single axis
+ * (cupyimg/skimage/filters/edges.py:128-200, which runs a 3-D magnitude as three dense convolutions plus seven whole-array
+ * passes; the mask: edges.py:55-65; csrc/edges.hip).  image: C-contiguous float32 / float64 (T; other dtypes:
+ * MI_ERR_UNSUPPORTED with nothing queued) of rank 1 .. 8; out: float64, the image's shape; mask: NULL or the ERODED mask as a
+ * bool / uint8 array of that shape; weights: naxes x 3^rank host doubles, per edge axis the dense kernel of edges.py:188-191
+ * already flipped for correlation, C order; mode / cval as for mi_correlate_nd (the reference drops cval, edges.py:192).
+ *     r_a = T(sum over the non-zero taps in C order, from 0.0, of double(x) * w), each product and sum rounded on its own
+ *     out = 0.0; for every edge axis in order: out = out + double(magnitude ? r_a * r_a : r_a), the square in T
+ *     magnitude: out = out / rank; out = sqrt(out)            (edges.py:197-199: by the rank, not by naxes)
+ *     mask:      out = out * double(mask)                     (edges.py:64: -x * 0 = -0.0, NaN * 0 = NaN)
+ *   magnitude == 0 takes exactly one edge axis (the signed response; 0.0 + -0.0 = +0.0 as in the reference).  Rank 2 and 3:
+ *   one launch (edge_fused_kernel: a box of the image with a one-sample halo in LDS, borders by index arithmetic, the
+ *   per-axis responses never in memory).  Other ranks, or after mi_debug_set_edges(.., 1): one mi_correlate_nd per edge axis
+ *   into a pooled scratch array plus per-voxel launches, the same bits.  Nothing synchronises.
+ * mi_edge_pair_magnitude (roberts, farid; edges.py:599-611, 759-769): out = sqrt(a * a + b * b) / T(divisor) on float32 /
+ *   float64 arrays of one shape and dtype T, every operation in T and rounded on its own; out may be a or b.
+ * mi_threshold_masks (apply_hysteresis_threshold, cupyimg/skimage/filters/thresholding.py:1218-1220): low is clipped to high
+ *   per voxel (the smaller of the two; a NaN of either stays), then mask_low = image > low, mask_high = image > high in one
+ *   launch, every operand as a double; image: any dtype but float16 and 64-bit integers; low /
+ *   high: NULL (then the scalar low_value / high_value) or float64 arrays of the image's shape; the masks: bool / uint8. */
+/* The stage of skimage.feature.canny between the smoothing and the hysteresis (cupyimg/skimage/feature/_canny.py:191-288, some
+ * forty masked temporaries there).  smoothed: C-contiguous float64 image (ny, nx) -- _canny.py:46-50 divides by a float64
+ * array, so the stage is float64 for every input dtype; eroded: the 3 x 3-eroded mask (border value 0, _canny.py:201-202) as
+ * bool / uint8; magnitude (float64), local_max, high_mask, low_mask (bool / uint8; the last two may both be NULL): outputs.
+ *     isobel, jsobel = scipy.ndimage.sobel(smoothed, axis = 0 / 1), mode 'reflect': two correlate1d passes in SciPy's order,
+ *                      d = x(l) * 0.0 + (x(l - 1) - x(l + 1)) * -1.0 along the axis, then d(l) * 2.0 + (d(l - 1) + d(l + 1)) * 1.0
+ *     magnitude      = sqrt(isobel * isobel + jsobel * jsobel), each operation rounded on its own (the reference calls
+ *                      hypot, whose last bit is libm's: the one deliberate deviation)
+ *     local_max      = eroded & (magnitude > 0) & [the class test], the four direction classes of _canny.py:210-275 with
+ *                      their predicates, w and `c2 * w + c1 * (1 - w) <= m` uncontracted, evaluated in the reference's
+ *                      order so that a later class overwrites an earlier one where predicates overlap
+ *     high_mask      = local_max & (magnitude >= high),  low_mask = local_max & (magnitude >= low)
+ *   One launch (canny_nms_kernel: a tile of `smoothed` with a halo of 2 in LDS -- one sample for Sobel, one for the neighbours'
+ *   magnitudes; magnitudes outside the image are computed from reflected samples and never consulted, because `eroded` is
+ *   false on the border ring).  After mi_debug_set_edges(.., 1): the Sobel responses by mi_correlate1d into pooled scratch
+ *   arrays and two launches with one thread per pixel straight from global memory, the same bits.
+ * mi_canny_threshold: the two masks alone from magnitude and local_max (use_quantiles: the thresholds come from the magnitude).
+ * mi_masked_copy: out = mask ? image : 0 on arrays of any dtype (_canny.py:47-48: a copy, so NaN and negative samples under the
+ *   mask leave no trace); out may be image.
+ * mi_canny_normalize: out = double(smoothed) / (bleed_over + DBL_EPSILON) (_canny.py:50), the sum and the quotient rounded on
+ *   their own; smoothed float32 / float64, bleed_over and out float64; out may be bleed_over (or smoothed, when float64). */
+int mi_masked_copy(const mi_array *image, const mi_array *mask, const mi_array *out, mi_stream stream);
+int mi_canny_normalize(const mi_array *smoothed, const mi_array *bleed_over, const mi_array *out, mi_stream stream);
+int mi_canny_nms(const mi_array *smoothed, const mi_array *eroded, const mi_array *magnitude, const mi_array *local_max,
+                 const mi_array *high_mask, const mi_array *low_mask, double high, double low, mi_stream stream);
+int mi_canny_threshold(const mi_array *magnitude, const mi_array *local_max, const mi_array *high_mask, const mi_array *low_mask,
+                       double high, double low, mi_stream stream);
+int mi_edge_filter(const mi_array *image, const mi_array *out, const mi_array *mask, const double *weights, int naxes,
+                   int magnitude, int mode, double cval, mi_stream stream);
+int mi_edge_pair_magnitude(const mi_array *a, const mi_array *b, const mi_array *out, double divisor, mi_stream stream);
+int mi_threshold_masks(const mi_array *image, const mi_array *low, const mi_array *high, double low_value, double high_value,
+                       const mi_array *mask_low, const mi_array *mask_high, mi_stream stream);
+
 /* ------------------------------------------------------------------ */
 /* K5: interpolation, spline order 0 and 1                              */
 /* ------------------------------------------------------------------ */
