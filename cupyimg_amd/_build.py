@@ -84,6 +84,7 @@ SOURCES = [
     ("morphsnakes.hip", ["-ffp-contract=off"]),
     ("tvl1.hip", ["-ffp-contract=off"]),
     ("edges.hip", ["-ffp-contract=off"]),
+    ("corners.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function",
           "-I" + os.path.join(os.path.dirname(HERE), "include")]

@@ -163,6 +163,8 @@ SIGNATURES = {
     "mi_canny_normalize": [_arr, _arr, _arr, _vp],
     "mi_edge_pair_magnitude": [_arr, _arr, _arr, _d, _vp],
     "mi_threshold_masks":[_arr, _arr, _arr, _d, _d, _arr, _arr, _vp],
+    "mi_structure_products": [_arr, _arr, _i, _i, _i, _d, _vp],
+    "mi_corner_response": [_arr, _arr, _arr, _i, _d, _d, _vp],
     "mi_map_coordinates": [_arr, _arr, _arr, _i, _i, _d, _vp],
     "mi_affine_transform": [_arr, _arr, _dp, _i, _i, _d, _vp],
     "mi_spline_pad": [_arr, _arr, _i, _i, _d, _vp],

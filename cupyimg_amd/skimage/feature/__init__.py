@@ -1,7 +1,9 @@
 """skimage.feature subset: the Hessian matrix and its eigenvalues (cupyimg/skimage/feature/corner.py:141-211, 260-458) on
-HIP kernels (csrc/ridges.hip), and the Canny edge detector (cupyimg/skimage/feature/_canny.py) with its Sobel, magnitude and
-non-maximum-suppression stage as one kernel (csrc/edges.hip)."""
+HIP kernels (csrc/ridges.hip), the Canny edge detector (cupyimg/skimage/feature/_canny.py) with its Sobel, magnitude and
+non-maximum-suppression stage as one kernel (csrc/edges.hip), and the structure tensor with the corner detectors built on it
+(corner.py:18-138, 384-425, 533-830; csrc/corners.hip)."""
 import ctypes
+import warnings
 
 import numpy as np
 
@@ -10,7 +12,8 @@ from ...scipy import ndimage as ndi
 from ...scipy.ndimage import _support as S
 from ..filters import _img_as_float
 
-__all__ = ["hessian_matrix", "hessian_matrix_eigvals", "structure_tensor_eigenvalues", "canny"]
+__all__ = ["hessian_matrix", "hessian_matrix_eigvals", "structure_tensor_eigenvalues", "canny", "structure_tensor",
+           "structure_tensor_eigvals", "corner_harris", "corner_shi_tomasi", "corner_foerstner", "corner_kitchen_rosenfeld"]
 
 
 def _as_float_device(image):
@@ -84,6 +87,162 @@ def hessian_matrix_eigvals(H_elems):
 def structure_tensor_eigenvalues(A_elems):
     """Eigenvalues of a structure tensor given by its upper-triangle elements, decreasing (corner.py:338-369)."""
     return _symmetric_compute_eigenvalues(A_elems)
+
+
+# ------------------------------------------------------------------ structure tensor and corner detectors (corner.py)
+_CORNER_KINDS = {"harris_k": 0, "harris_eps": 1, "shi_tomasi": 2, "foerstner": 3, "kitchen_rosenfeld": 4}
+
+
+def _ndim_of(image):
+    return image.ndim if isinstance(image, (core.ndarray, np.ndarray)) else np.ndim(image)
+
+
+def _row_block(rows, size, dtype):
+    """an uninitialised (rows, size) block whose rows start on 16-byte boundaries (the rows of an odd-sized image are padded),
+    so that a row is as good an input or output of the fused filters as an array of its own"""
+    per16 = 16 // np.dtype(dtype).itemsize
+    padded = -(-size // per16) * per16
+    return core.empty((rows, padded), dtype)[:, :size]
+
+
+def _rows_as_images(block, shape):
+    return [block[e].reshape(shape) for e in range(block.shape[0])]
+
+
+def _sobel_block(image, products, reverse, mode, cval, out=None):
+    """mi_structure_products: the Sobel derivatives of every axis (products false) or their pairwise products as the rows of
+    one block"""
+    rows = image.ndim * (image.ndim + 1) // 2 if products else image.ndim
+    if out is None:
+        out = _row_block(rows, image.size, image.dtype)
+    idesc, odesc = image._desc(), out._desc()
+    S.check(S.lib().mi_structure_products(ctypes.byref(idesc), ctypes.byref(odesc), int(products), int(reverse), S.mode_code(mode),
+                                          float(cval), None), ValueError)
+    return out
+
+
+def _check_structure_args(ndim, sigma, mode, order):
+    """(order, sigmas): every check of structure_tensor's arguments, before anything touches the device"""
+    if order not in (None, "rc", "xy"):
+        raise ValueError("order must be 'rc' or 'xy', got {!r}".format(order))
+    if order == "xy" and ndim > 2:
+        raise ValueError('Only "rc" order is supported for dim > 2.')
+    if ndim < 1 or ndim > _lib.MI_MAX_NDIM:
+        raise ValueError("arrays of rank 1 to {}".format(_lib.MI_MAX_NDIM))
+    S.check_mode(mode)
+    sigmas = [float(s) for s in S.normalize_sequence(sigma, ndim)]
+    if order is None:
+        if ndim == 2:
+            warnings.warn('deprecation warning: the default order of the structure tensor values will be "row-column" instead of '
+                          '"xy" starting in skimage version 0.20. Use order="rc" or order="xy" to set this explicitly.  (Specify '
+                          'order="xy" to maintain the old behavior.)', category=FutureWarning, stacklevel=3)
+            order = "xy"
+        else:
+            order = "rc"
+    return order, sigmas
+
+
+def _structure_tensor_block(image, sigmas, mode, cval, order):
+    image = core.ascontiguousarray(_as_float_device(image))
+    products = _sobel_block(image, True, order == "xy", mode, cval)
+    out = _row_block(products.shape[0], image.size, image.dtype)
+    if image.size:
+        for src, dst in zip(_rows_as_images(products, image.shape), _rows_as_images(out, image.shape)):
+            ndi.gaussian_filter(src, sigmas, output=dst, mode=mode, cval=cval)
+    return out, image.shape
+
+
+def structure_tensor(image, sigma=1, mode="constant", cval=0, order=None):
+    """The structure tensor's upper-triangle elements gaussian_filter(d_i * d_j, sigma) as a list of device arrays, d_a the Sobel
+    derivative along axis a, for (i, j) in combinations_with_replacement(axes, 2) (corner.py:46-138).  `order` applies in 2-D
+    only: 'rc' gives Arr, Arc, Acc, 'xy' gives Axx, Axy, Ayy; None means 'xy' in 2-D (with a FutureWarning, as in the
+    reference) and 'rc' otherwise.  `sigma` is a scalar or one value per axis.
+
+    One launch (mi_structure_products) reads the image once and writes the products; the derivatives never exist in memory.
+    Every derivative is scipy.ndimage.sobel's own arithmetic (each 1-D pass accumulated in double and rounded to the image
+    dtype), the products are formed in the image dtype, and this library's gaussian_filter smooths each of them: the result
+    is bit-identical to that filter applied to the products of tests/helpers/corner_ref.py.  The elements are views of one
+    (n_elements, image.size) block.  Peak memory in 3-D: the image plus two blocks of six volumes (the products and the
+    smoothed elements).  Integers are scaled to float64 (img_as_float), float16 is computed in float32."""
+    order, sigmas = _check_structure_args(_ndim_of(image), sigma, mode, order)
+    out, shape = _structure_tensor_block(image, sigmas, mode, float(cval), order)
+    return _rows_as_images(out, shape)
+
+
+def structure_tensor_eigvals(Axx, Axy, Ayy):
+    """(l1, l2), the larger and the smaller eigenvalue of the 2 x 2 structure tensor (corner.py:384-425; deprecated there in
+    favour of structure_tensor_eigenvalues, with the same FutureWarning here)."""
+    warnings.warn("deprecation warning: the function structure_tensor_eigvals is deprecated and will be removed in version 0.20. "
+                  "Please use structure_tensor_eigenvalues instead.", category=FutureWarning, stacklevel=2)
+    if any(_ndim_of(e) != 2 for e in (Axx, Axy, Ayy)):
+        raise ValueError("structure_tensor_eigvals takes the three elements of a 2-D structure tensor")
+    eigs = _symmetric_compute_eigenvalues([Axx, Axy, Ayy])
+    return eigs[0], eigs[1]
+
+
+def _require_2d(image, name):
+    if _ndim_of(image) != 2:
+        raise ValueError("{} takes 2-dimensional images".format(name))
+
+
+def _corner_response(block, shape, kind, out_dtype, k=0.0, eps=0.0):
+    """mi_corner_response: one pointwise launch over the rows of `block`"""
+    outs = [core.empty(shape, out_dtype) for _ in range(2 if kind == "foerstner" else 1)]
+    bdesc, descs = block._desc(), [o._desc() for o in outs]
+    S.check(S.lib().mi_corner_response(ctypes.byref(bdesc), ctypes.byref(descs[0]), ctypes.byref(descs[1]) if len(descs) > 1 else None,
+                                       _CORNER_KINDS[kind], float(k), float(eps), None), ValueError)
+    return outs
+
+
+def corner_harris(image, method="k", k=0.05, eps=1e-6, sigma=1):
+    """Harris corner response, 2-D (corner.py:593-671): det(A) - k * trace(A)^2 for method 'k', 2 * det(A) / (trace(A) + eps)
+    for 'eps', A = structure_tensor(image, sigma, order='rc') with its default mode 'constant'.  One pointwise launch after the
+    tensor, every operation in the elements' dtype in the reference's order (`k` and `eps` act as weak scalars: a float32
+    tensor gives a float32 response)."""
+    _require_2d(image, "corner_harris")
+    if method not in ("k", "eps"):
+        raise ValueError("method must be 'k' or 'eps', got {!r}".format(method))
+    _, sigmas = _check_structure_args(2, sigma, "constant", "rc")
+    block, shape = _structure_tensor_block(image, sigmas, "constant", 0, "rc")
+    return _corner_response(block, shape, "harris_" + method, block.dtype, k, eps)[0]
+
+
+def corner_shi_tomasi(image, sigma=1):
+    """Shi-Tomasi (Kanade-Tomasi) corner response, 2-D (corner.py:674-743), exactly what the reference computes:
+    (Arr + Acc) - sqrt((Arr - Acc)^2 + 4 * Arc * Arc) / 2, twice the smaller eigenvalue of the structure tensor."""
+    _require_2d(image, "corner_shi_tomasi")
+    _, sigmas = _check_structure_args(2, sigma, "constant", "rc")
+    block, shape = _structure_tensor_block(image, sigmas, "constant", 0, "rc")
+    return _corner_response(block, shape, "shi_tomasi", block.dtype)[0]
+
+
+def corner_foerstner(image, sigma=1):
+    """Foerstner corner measures (w, q), 2-D (corner.py:746-830): w = det(A) / trace(A), q = 4 * det(A) / trace(A)^2 where the
+    trace is not 0, else 0; the quotients are formed in the tensor's dtype and stored as float64, as in the reference."""
+    _require_2d(image, "corner_foerstner")
+    _, sigmas = _check_structure_args(2, sigma, "constant", "rc")
+    block, shape = _structure_tensor_block(image, sigmas, "constant", 0, "rc")
+    w, q = _corner_response(block, shape, "foerstner", np.float64)
+    return w, q
+
+
+def corner_kitchen_rosenfeld(image, mode="constant", cval=0):
+    """Kitchen-Rosenfeld corner response, 2-D (corner.py:533-590): (imxx * imy^2 + imyy * imx^2 - 2 * imxy * imx * imy) /
+    (imx^2 + imy^2) where the denominator is not 0, else 0, float64; imx, imy the Sobel derivatives of the image along the
+    two axes and imxx, imxy, imyy theirs.  Three derivative launches (image, imx, imy) and one response launch.
+
+    Deviation: the reference feeds integer images unconverted into ndi.sobel here, where they wrap; this function converts
+    the image like the other detectors do (integers scaled to float64, float16 computed in float32)."""
+    _require_2d(image, "corner_kitchen_rosenfeld")
+    S.check_mode(mode)
+    cval = float(cval)
+    image = core.ascontiguousarray(_as_float_device(image))
+    block = _row_block(6, image.size, image.dtype)
+    if image.size:
+        _sobel_block(image, False, False, mode, cval, out=block[0:2])
+        _sobel_block(block[0].reshape(image.shape), False, False, mode, cval, out=block[2:4])
+        _sobel_block(block[1].reshape(image.shape), False, False, mode, cval, out=block[4:6])
+    return _corner_response(block, image.shape, "kitchen_rosenfeld", np.float64)[0]
 
 
 # ------------------------------------------------------------------ canny (_canny.py)

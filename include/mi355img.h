@@ -753,6 +753,35 @@ int mi_edge_pair_magnitude(const mi_array *a, const mi_array *b, const mi_array 
 int mi_threshold_masks(const mi_array *image, const mi_array *low, const mi_array *high, double low_value, double high_value,
                        const mi_array *mask_low, const mi_array *mask_high, mi_stream stream);
 
+/* skimage.feature.structure_tensor and the corner detectors (cupyimg/skimage/feature/corner.py:18-43, 125-136, 566-590, 658-671,
+ * 728-743, 812-830; csrc/corners.hip).  image: C-contiguous float32 / float64 (T; other dtypes: MI_ERR_UNSUPPORTED with nothing
+ * queued) of rank 1 .. 8.
+ * mi_structure_products: out is a block of T with `rank` rows (products == 0) or rank (rank + 1) / 2 rows (products != 0) of
+ *   image.size elements; its rows are contiguous and a whole number of elements apart (they may be padded).
+ *     d_a  = scipy.ndimage.sobel(image, axis = a, mode, cval) in SciPy's own arithmetic: correlate1d with [-1, 0, 1] along a,
+ *            then with [1, 2, 1] along every other axis in ascending order, every pass accumulated in double as
+ *            x(l) * 0.0 + (x(l - 1) - x(l + 1)) * -1.0   or   d(l) * 2.0 + (d(l - 1) + d(l + 1)) * 1.0   (the `* 0.0` term stays: an
+ *            infinite centre gives NaN) and rounded to T before the next pass reads it
+ *     mode 'constant': every pass extends its own input line with the double cval, so an intermediate outside the array along the
+ *            pass axis IS cval (this is not the Sobel filter of the cval-padded image); every other mode: the index map
+ *     products == 0: row a = d_a;  products != 0: row e = d_i * d_j in T, (i, j) the e-th of combinations_with_replacement(axes, 2)
+ *     reverse != 0 (2-D only, order 'xy'): the derivatives are reversed first
+ *   Rank 2 and 3: one launch (st_fused_kernel: a box of the image with a one-sample halo in LDS, every axis's rounded passes from
+ *   registers; the derivatives never exist in memory on the product route).  Other ranks, or after mi_debug_set_corners(.., 1):
+ *   one st_pass_kernel launch per pass through pooled scratch arrays and st_product_kernel, the same bits.
+ * mi_corner_response: one pointwise launch over elems, a (3, size) block Arr, Arc, Acc of T (kind 4: a (6, size) block imx, imy,
+ *   imxx, imxy, imyx, imyy; row 4 is not read), rows as above; every operation in T, in the reference's order, rounded on its own:
+ *     0 harris 'k':   detA = Arr * Acc; detA -= Arc * Arc; traceA = Arr + Acc; out0 = detA - (T(k) * traceA) * traceA
+ *     1 harris 'eps': out0 = (2 * detA) / (traceA + T(eps))
+ *     2 shi-tomasi:   out0 = (Arr + Acc) - sqrt((Arr - Acc)^2 + (4 * Arc) * Arc) / 2
+ *     3 foerstner:    out0 = w = detA / traceA, out1 = q = (4 * detA) / (traceA * traceA) where traceA != 0, else 0 (float64 outputs)
+ *     4 kitchen-rosenfeld: out0 = ((imxx * imy) * imy + (imyy * imx) * imx - ((2 * imxy) * imx) * imy) / (imx * imx + imy * imy)
+ *                     where the denominator is not 0, else 0 (a float64 output)
+ *   out0 (out1: kind 3 only, else NULL): C-contiguous, image.size elements, of T for kinds 0 .. 2 and float64 for 3 and 4.
+ * Nothing synchronises and nothing is read by the host. */
+int mi_structure_products(const mi_array *image, const mi_array *out, int products, int reverse, int mode, double cval, mi_stream stream);
+int mi_corner_response(const mi_array *elems, const mi_array *out0, const mi_array *out1, int kind, double k, double eps, mi_stream stream);
+
 /* ------------------------------------------------------------------ */
 /* K5: interpolation, spline order 0 and 1                              */
 /* ------------------------------------------------------------------ */
