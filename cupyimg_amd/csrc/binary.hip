@@ -90,7 +90,6 @@ binary3_kernel(const T *__restrict__ in, void *__restrict__ out, int out_dt, con
 }  // namespace mi
 
 namespace mi {
-void note_kernel(const char *fmt, ...);      // separable3d.hip: which kernel a call dispatched (mi_debug_last_kernel)
 int binary3_tiled(const mi_array *in, const mi_array *out, const uint8_t *structure, const int64_t *sshape,
                   const int *origins, const mi_array *mask, int border_value, int invert, int32_t *changed,
                   hipStream_t s);   // binary3d.hip

@@ -71,6 +71,9 @@ struct Knob {
 hipStream_t resolve_stream(mi_stream s);   // NULL -> per-device default stream
 int device_cus();                          // compute units of the CURRENT device (cached per device, thread safe)
 int current_device_slot();                 // hipGetDevice() folded into 0 .. 63 (0 when it cannot be asked)
+// remembers (per host thread) which kernel a call dispatched: mi_debug_last_kernel (tests and bench.py name the kernel
+// they ran from this, not from a literal); defined in separable3d.hip
+void note_kernel(const char *fmt, ...);
 
 // "done once" flag of something that is PER DEVICE -- hipFuncSetAttribute(MaxDynamicSharedMemorySize) above all: a process
 // that drives a second device must set it there too (r4 advisor finding: one process-wide `static bool` left the second

@@ -17,7 +17,7 @@
 // the array ALONG THE PASS AXIS is cval, not a derivative of constants, so the kernel substitutes cval per pass from the
 // voxel's coordinates.
 //
-// st_fused_kernel<T, RANK, PRODUCTS, CONST>: the skeleton of edge_fused_kernel (edges.hip).  A workgroup of 256 threads owns core
+// st_fused_kernel<T, RANK, PRODUCTS, CONST>: the box scaffolding of skimage_common.hpp.  A workgroup of 256 threads owns core
 // boxes of t_z x t_y x t_x voxels (RANK 2: t_y x t_x pixels), stages each with a one-sample halo in LDS through the boundary map,
 // then a wave takes rows of the box with its lanes along x: the 3^RANK samples go to registers once and serve the three (two)
 // rounded passes of every axis.  It stores the RANK derivatives (PRODUCTS false) or the RANK (RANK + 1) / 2 products as
@@ -29,22 +29,16 @@
 //
 // corner_response_kernel<T, KIND, VEC>: one pointwise launch over the tensor elements Arr, Arc, Acc (Kitchen-Rosenfeld: imx, imy,
 // imxx, imxy, imyy), 16-byte accesses where the rows are aligned, every operation in the order and dtype of corner.py.
-#include "common.hpp"
-#include <algorithm>
+#include "skimage_common.hpp"
 
 namespace mi {
-void note_kernel(const char *fmt, ...);      // separable3d.hip: which kernel a call dispatched (mi_debug_last_kernel)
 
 constexpr int kStNT = 256;
 constexpr int kStLdsBytes = 32 * 1024;
-constexpr int kStMaxGrid = 1 << 20;
 
 static Knob g_st_small{0}, g_st_generic{0};
 
-struct StParams {
-    int n[3];           // nz, ny, nx (RANK 2: nz = 1)
-    int t[3];           // the core box
-    int nt[3];          // boxes per axis
+struct StParams : BoxDims {
     int mode;           // filter_mode()
     int reverse;        // order 'xy': the derivatives are taken last axis first
     double cval;
@@ -72,28 +66,13 @@ __global__ void __launch_bounds__(kStNT)
 st_fused_kernel(const T *__restrict__ in, T *__restrict__ out, const StParams p, const int64_t nboxes)
 {
     __shared__ T tile[kStLdsBytes / sizeof(T)];
-    constexpr int HZ = RANK == 3 ? 1 : 0;
     constexpr int KZ = RANK == 3 ? 3 : 1;
-    const int ez = p.t[0] + 2 * HZ, ey = p.t[1] + 2, ex = p.t[2] + 2;
+    const int ey = p.t[1] + 2, ex = p.t[2] + 2;         // rows and columns of the staged box
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int64_t box = blockIdx.x; box < nboxes; box += gridDim.x) {
-        const int bx = (int)(box % p.nt[2]);
-        const int64_t rest = box / p.nt[2];
-        const int by = (int)(rest % p.nt[1]), bz = (int)(rest / p.nt[1]);
-        const int z0 = bz * p.t[0], y0 = by * p.t[1], x0 = bx * p.t[2];
-        // stage the box and its halo; a staged index is always inside the array (the map of 'constant' gives -1: a zero
-        // is staged and never used)
-        for (int row = wave; row < ez * ey; row += kStNT / 64) {
-            const int sz = row / ey, sy = row - sz * ey;
-            const int gz = HZ ? bmap_near<int>(z0 + sz - 1, p.n[0], p.mode) : 0;
-            const int gy = bmap_near<int>(y0 + sy - 1, p.n[1], p.mode);
-            for (int sx = lane; sx < ex; sx += 64) {
-                const int gx = bmap_near<int>(x0 + sx - 1, p.n[2], p.mode);
-                T v = T(0);
-                if (gz >= 0 && gy >= 0 && gx >= 0) v = in[((int64_t)gz * p.n[1] + gy) * p.n[2] + gx];
-                tile[row * ex + sx] = v;
-            }
-        }
+        int z0, y0, x0;
+        box_origin(p, box, z0, y0, x0);
+        stage_halo1_box<T, RANK, kStNT>(tile, in, p, p.mode, z0, y0, x0);
         __syncthreads();
         for (int row = wave; row < p.t[0] * p.t[1]; row += kStNT / 64) {
             const int cz = row / p.t[1], cy = row - cz * p.t[1];
@@ -209,13 +188,6 @@ st_product_kernel(const T *__restrict__ d, T *__restrict__ out, int64_t total, i
 // ------------------------------------------------------------------ the detector responses (corner.py), every operation in T
 enum { kCrHarrisK = 0, kCrHarrisEps = 1, kCrShiTomasi = 2, kCrFoerstner = 3, kCrKitchenRosenfeld = 4 };
 
-template <typename T>
-__device__ __forceinline__ T st_sqrt(T x)
-{
-    if constexpr (std::is_same<T, float>::value) return __builtin_sqrtf(x);
-    else return __builtin_sqrt(x);
-}
-
 // r0 (and r1 for Foerstner) of one pixel; a .. e: Arr, Arc, Acc (Kitchen-Rosenfeld: imx, imy, imxx, imxy, imyy)
 template <typename T, int KIND, typename O>
 __device__ __forceinline__ void corner_point(T a, T b, T c, T d, T e, T k, T eps, O &r0, O &r1)
@@ -241,7 +213,7 @@ __device__ __forceinline__ void corner_point(T a, T b, T c, T d, T e, T k, T eps
         T tmp2 = T(4) * b;
         tmp2 = tmp2 * b;
         tmp = tmp + tmp2;
-        tmp = st_sqrt<T>(tmp);
+        tmp = sqrt_t<T>(tmp);
         tmp = tmp / T(2);
         T r = a + c;
         r = r - tmp;
@@ -313,43 +285,23 @@ corner_response_kernel(const T *__restrict__ elems, int64_t stride, void *__rest
 
 static int st_grid(int64_t n)
 {
-    return (int)std::max<int64_t>(1, std::min<int64_t>((n + kStNT - 1) / kStNT, 8192));
+    return capped_grid(n, kStNT, 8192);
 }
 
 template <typename T, int RANK>
 static int st_fused(const mi_array *image, T *out, int64_t ostride, int products, int reverse, int mode, double cval, hipStream_t s)
 {
-    const bool small = g_st_small != 0;
     StParams p;
     memset(&p, 0, sizeof(p));
-    for (int d = 0; d < 3; d++) {
-        const int64_t n = d < 3 - RANK ? 1 : image->shape[d - (3 - RANK)];
-        if (n >= ((int64_t)1 << 30)) return MI_ERR_UNSUPPORTED;
-        p.n[d] = (int)n;
-    }
-    if (RANK == 3) {
-        p.t[0] = small ? 2 : (sizeof(T) == 4 ? 8 : 4);
-        p.t[1] = small ? 3 : 8;
-    } else {
-        p.t[0] = 1;
-        p.t[1] = small ? 3 : 32;
-    }
-    p.t[2] = small ? 5 : 64;
-    for (int d = 0; d < 3; d++) {
-        p.t[d] = std::min(p.t[d], p.n[d]);
-        p.nt[d] = (p.n[d] + p.t[d] - 1) / p.t[d];
-    }
-    const int64_t staged = (int64_t)(p.t[0] + (RANK == 3 ? 2 : 0)) * (p.t[1] + 2) * (p.t[2] + 2);
-    if (staged * (int64_t)sizeof(T) > kStLdsBytes) {
-        set_error("structure_products: the staged box does not fit the kernel's LDS");
-        return MI_ERR_INTERNAL;
-    }
+    int64_t nboxes;
+    const int rc = plan_halo1_box(image, g_st_small != 0, kStLdsBytes, &p, &nboxes);
+    if (rc == MI_ERR_INTERNAL) set_error("structure_products: the staged box does not fit the kernel's LDS");
+    if (rc) return rc;
     p.mode = mode;
     p.reverse = reverse;
     p.cval = cval;
     p.ostride = ostride;
-    const int64_t nboxes = (int64_t)p.nt[0] * p.nt[1] * p.nt[2];
-    const int grid = (int)std::min<int64_t>(nboxes, kStMaxGrid);
+    const int grid = box_grid(nboxes);
     const T *in = (const T *)image->data;
 #define ST_LAUNCH(P, C) hipLaunchKernelGGL((st_fused_kernel<T, RANK, P, C>), dim3(grid), dim3(kStNT), 0, s, in, out, p, nboxes)
     if (products) {

@@ -24,22 +24,16 @@
 //
 // Ranks 1 and >= 4, or after mi_debug_set_edges(.., 1): the same arithmetic as one mi_correlate_nd per edge axis into a
 // scratch array of T, edge_accumulate_kernel after each and edge_finish_kernel at the end (one thread per voxel).
-#include "common.hpp"
-#include <algorithm>
+#include "skimage_common.hpp"
 
 namespace mi {
-void note_kernel(const char *fmt, ...);      // separable3d.hip: which kernel a call dispatched (mi_debug_last_kernel)
 
 constexpr int kEdNT = 256;
 constexpr int kEdLdsBytes = 32 * 1024;
-constexpr int kEdMaxGrid = 1 << 20;
 
 static Knob g_ed_small{0}, g_ed_generic{0};
 
-struct EdParams {
-    int n[3];           // nz, ny, nx (RANK 2: nz = 1)
-    int t[3];           // the core box
-    int nt[3];          // boxes per axis
+struct EdParams : BoxDims {
     int na;             // edge axes
     int edim[3];        // per edge axis: the axis (0 .. 2 of nz, ny, nx) whose centre plane holds the zero weights
     int magnitude;
@@ -74,26 +68,12 @@ edge_fused_kernel(const T *__restrict__ in, const uint8_t *__restrict__ mask, do
     constexpr int HZ = RANK == 3 ? 1 : 0;
     constexpr int KZ = RANK == 3 ? 3 : 1;
     constexpr int NTAP = KZ * 9;
-    const int ez = p.t[0] + 2 * HZ, ey = p.t[1] + 2, ex = p.t[2] + 2;
+    const int ey = p.t[1] + 2, ex = p.t[2] + 2;         // rows and columns of the staged box
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int64_t box = blockIdx.x; box < nboxes; box += gridDim.x) {
-        const int bx = (int)(box % p.nt[2]);
-        const int64_t rest = box / p.nt[2];
-        const int by = (int)(rest % p.nt[1]), bz = (int)(rest / p.nt[1]);
-        const int z0 = bz * p.t[0], y0 = by * p.t[1], x0 = bx * p.t[2];
-        // stage the box and its halo; a staged index is always inside the array (the map of 'constant' gives -1: a zero
-        // is staged and never used)
-        for (int row = wave; row < ez * ey; row += kEdNT / 64) {
-            const int sz = row / ey, sy = row - sz * ey;
-            const int gz = HZ ? bmap_near<int>(z0 + sz - 1, p.n[0], p.mode) : 0;
-            const int gy = bmap_near<int>(y0 + sy - 1, p.n[1], p.mode);
-            for (int sx = lane; sx < ex; sx += 64) {
-                const int gx = bmap_near<int>(x0 + sx - 1, p.n[2], p.mode);
-                T v = T(0);
-                if (gz >= 0 && gy >= 0 && gx >= 0) v = in[((int64_t)gz * p.n[1] + gy) * p.n[2] + gx];
-                tile[row * ex + sx] = v;
-            }
-        }
+        int z0, y0, x0;
+        box_origin(p, box, z0, y0, x0);
+        stage_halo1_box<T, RANK, kEdNT>(tile, in, p, p.mode, z0, y0, x0);
         __syncthreads();
         for (int row = wave; row < p.t[0] * p.t[1]; row += kEdNT / 64) {
             const int cz = row / p.t[1], cy = row - cz * p.t[1];
@@ -173,8 +153,7 @@ edge_pair_kernel(const T *__restrict__ a, const T *__restrict__ b, T *__restrict
         const T p = a[i] * a[i];
         T q = b[i] * b[i];
         q = q + p;
-        if constexpr (std::is_same<T, float>::value) q = __builtin_sqrtf(q);
-        else q = __builtin_sqrt(q);
+        q = sqrt_t<T>(q);
         out[i] = q / divisor;
     }
 }
@@ -197,14 +176,13 @@ threshold_masks_kernel(const void *__restrict__ image, int dtype, const double *
 
 static int ed_grid(int64_t n)
 {
-    return (int)std::max<int64_t>(1, std::min<int64_t>((n + kEdNT - 1) / kEdNT, 8192));
+    return capped_grid(n, kEdNT, 8192);
 }
 
 template <typename T, int RANK, bool FMA>
-static int ed_launch(const mi_array *image, const uint8_t *mask, double *out, const EdParams &p, hipStream_t s)
+static int ed_launch(const mi_array *image, const uint8_t *mask, double *out, const EdParams &p, int64_t nboxes, hipStream_t s)
 {
-    const int64_t nboxes = (int64_t)p.nt[0] * p.nt[1] * p.nt[2];
-    const int grid = (int)std::min<int64_t>(nboxes, kEdMaxGrid);
+    const int grid = box_grid(nboxes);
     if (p.mode == MI_MODE_CONSTANT)
         hipLaunchKernelGGL((edge_fused_kernel<T, RANK, true, FMA>), dim3(grid), dim3(kEdNT), 0, s, (const T *)image->data, mask, out, p, nboxes);
     else
@@ -221,29 +199,12 @@ static int ed_fused(const mi_array *image, const uint8_t *mask, double *out, con
                     int mode, double cval, hipStream_t s)
 {
     const int rank = image->ndim;
-    const bool f32 = image->dtype == MI_F32, small = g_ed_small != 0;
+    const bool f32 = image->dtype == MI_F32;
     EdParams p;
     memset(&p, 0, sizeof(p));
     const int ntap = rank == 3 ? 27 : 9;
-    for (int d = 0; d < 3; d++) {
-        const int64_t n = d < 3 - rank ? 1 : image->shape[d - (3 - rank)];
-        if (n >= ((int64_t)1 << 30)) return MI_ERR_UNSUPPORTED;
-        p.n[d] = (int)n;
-    }
-    if (rank == 3) {
-        p.t[0] = small ? 2 : (f32 ? 8 : 4);
-        p.t[1] = small ? 3 : 8;
-    } else {
-        p.t[0] = 1;
-        p.t[1] = small ? 3 : 32;
-    }
-    p.t[2] = small ? 5 : 64;
-    for (int d = 0; d < 3; d++) {
-        p.t[d] = std::min(p.t[d], p.n[d]);
-        p.nt[d] = (p.n[d] + p.t[d] - 1) / p.t[d];
-    }
-    const int64_t staged = (int64_t)(p.t[0] + (rank == 3 ? 2 : 0)) * (p.t[1] + 2) * (p.t[2] + 2);
-    if (staged * (int64_t)dtype_size(image->dtype) > kEdLdsBytes) return MI_ERR_INTERNAL;
+    int64_t nboxes;
+    if (const int rc = plan_halo1_box(image, g_ed_small != 0, kEdLdsBytes, &p, &nboxes)) return rc;
     p.na = naxes;
     p.magnitude = magnitude;
     p.mode = mode;
@@ -269,11 +230,11 @@ static int ed_fused(const mi_array *image, const uint8_t *mask, double *out, con
         }
     }
     if (rank == 3) {
-        if (exact) return ed_launch<float, 3, true>(image, mask, out, p, s);
-        return f32 ? ed_launch<float, 3, false>(image, mask, out, p, s) : ed_launch<double, 3, false>(image, mask, out, p, s);
+        if (exact) return ed_launch<float, 3, true>(image, mask, out, p, nboxes, s);
+        return f32 ? ed_launch<float, 3, false>(image, mask, out, p, nboxes, s) : ed_launch<double, 3, false>(image, mask, out, p, nboxes, s);
     }
-    if (exact) return ed_launch<float, 2, true>(image, mask, out, p, s);
-    return f32 ? ed_launch<float, 2, false>(image, mask, out, p, s) : ed_launch<double, 2, false>(image, mask, out, p, s);
+    if (exact) return ed_launch<float, 2, true>(image, mask, out, p, nboxes, s);
+    return f32 ? ed_launch<float, 2, false>(image, mask, out, p, nboxes, s) : ed_launch<double, 2, false>(image, mask, out, p, nboxes, s);
 }
 
 // ------------------------------------------------------------------ the Canny stage (_canny.py:191-288), float64
@@ -501,7 +462,7 @@ extern "C" int mi_canny_nms(const mi_array *smoothed, const mi_array *eroded, co
         p.nty = (p.ny + p.ty - 1) / p.ty;
         p.ntx = (p.nx + p.tx - 1) / p.tx;
         const int64_t ntiles = (int64_t)p.nty * p.ntx;
-        const int grid = (int)std::min<int64_t>(ntiles, kEdMaxGrid);
+        const int grid = box_grid(ntiles);
         hipLaunchKernelGGL(canny_nms_kernel, dim3(grid), dim3(kEdNT), 0, s, (const double *)smoothed->data, (const uint8_t *)eroded->data,
                            (double *)magnitude->data, (uint8_t *)local_max->data, hm, lo, high, low, p, ntiles);
         MI_HIP(hipGetLastError());

@@ -24,7 +24,6 @@
 #include <algorithm>
 
 namespace mi {
-void note_kernel(const char *fmt, ...);      // separable3d.hip: which kernel a call dispatched (mi_debug_last_kernel)
 
 constexpr int kClNd = MI_CLAHE_MAX_NDIM;
 constexpr int kClMapNT = 512;                // clahe_maps_kernel: 8 waves

@@ -21,8 +21,6 @@
 
 namespace mi {
 
-void note_kernel(const char *fmt, ...);      // separable3d.hip: which kernel a call dispatched (mi_debug_last_kernel)
-
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 struct FastInterpParams {

@@ -31,8 +31,6 @@
 
 namespace mi {
 
-void note_kernel(const char *fmt, ...);      // separable3d.hip: which kernel a call dispatched (mi_debug_last_kernel)
-
 static Knob g_label_generic{0};
 
 constexpr int kLabelTile = 4096;             // voxels per tile of the LDS kernel

@@ -20,8 +20,6 @@
 
 namespace mi {
 
-void note_kernel(const char *fmt, ...);      // separable3d.hip: which kernel a call dispatched (mi_debug_last_kernel)
-
 constexpr int kLdsSlots = 1024;
 constexpr int kLdsCom = 2048;             // LDS accumulators of center_of_mass: slots x axes
 

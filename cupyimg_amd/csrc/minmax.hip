@@ -12,7 +12,6 @@
 //     tap in the input dtype (unsigned types wrap), then compares as double.
 #include "nd_common.hpp"
 
-namespace mi { void note_kernel(const char *fmt, ...); }      // runtime.hip
 namespace mi {
 
 template <typename T, typename I>

@@ -33,11 +33,9 @@
 // fixed order and writes c0 and c1 (rounded to T) into the state block.
 // snake_hist_kernel / snake_pick_kernel: radix select (8 bits a pass) of two neighbouring order statistics for
 // threshold = "auto".
-#include "common.hpp"
-#include <algorithm>
+#include "skimage_common.hpp"
 
 namespace mi {
-void note_kernel(const char *fmt, ...);      // separable3d.hip: which kernel a call dispatched (mi_debug_last_kernel)
 
 constexpr int kSnNT = 256;
 constexpr int kSnMaxStages = 8;              // stages of one launch at most (LDS: two byte buffers of the box plus halo)
@@ -421,10 +419,7 @@ snake_invgrad_kernel(const T *__restrict__ gm, T *__restrict__ out, int64_t tota
 {
     for (int64_t i = (int64_t)blockIdx.x * kSnNT + threadIdx.x; i < total; i += (int64_t)gridDim.x * kSnNT) {
         const T s = T(1) + alpha * gm[i];
-        T r;
-        if constexpr (sizeof(T) == 4) r = __builtin_sqrtf(s);
-        else r = __builtin_sqrt(s);
-        out[i] = T(1) / r;
+        out[i] = T(1) / sqrt_t<T>(s);
     }
 }
 
@@ -437,7 +432,7 @@ static inline void sn_count(int n = 1) { g_sn_launches.fetch_add(n, std::memory_
 
 static int sn_grid(int64_t total)
 {
-    return (int)std::max<int64_t>(1, std::min<int64_t>((total + kSnNT - 1) / kSnNT, kSnGenericMaxGrid));
+    return capped_grid(total, kSnNT, kSnGenericMaxGrid);
 }
 
 static int sn_check_u(const mi_array *u, const char *name, const mi_array *like)

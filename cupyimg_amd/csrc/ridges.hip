@@ -28,21 +28,13 @@
 // and updates `out` in place, so G is read once and the Hessian, the eigenvalues and a per-scale stack never exist in memory.
 // hessian_generic_kernel + eig_generic_kernel: the same arithmetic with one thread per voxel and the elements in memory,
 // any rank; the route of mi_debug_set_ridges(.., .., 1).
-#include "common.hpp"
-#include <algorithm>
+#include "skimage_common.hpp"
 #include <limits>
 
 namespace mi {
-void note_kernel(const char *fmt, ...);      // separable3d.hip: which kernel a call dispatched (mi_debug_last_kernel)
 
 constexpr int kRgNT = 256;
 
-template <typename T>
-__device__ __forceinline__ T rg_sqrt(T v)
-{
-    if constexpr (std::is_same<T, float>::value) return __builtin_sqrtf(v);
-    else return __builtin_sqrt(v);
-}
 template <typename T>
 __device__ __forceinline__ T rg_exp(T v)
 {
@@ -100,7 +92,7 @@ __device__ __forceinline__ void rg_eigvals(const T *e, T *lam)
         T tmp2 = m00 - m11;
         tmp2 = tmp2 * tmp2;
         tmp2 = tmp2 + tmp1;
-        tmp2 = rg_sqrt<T>(tmp2);
+        tmp2 = sqrt_t<T>(tmp2);
         tmp2 = tmp2 / T(2);
         tmp1 = m00 + m11;
         tmp1 = tmp1 / T(2);
@@ -140,12 +132,12 @@ __device__ __forceinline__ void rg_eigvals(const T *e, T *lam)
                         const T th2 = theta * theta;
                         T t;
                         if (th2 <= std::numeric_limits<T>::max()) {
-                            t = T(1) / (rg_abs<T>(theta) + rg_sqrt<T>(th2 + T(1)));
+                            t = T(1) / (rg_abs<T>(theta) + sqrt_t<T>(th2 + T(1)));
                             if (theta < T(0)) t = -t;
                         } else {
                             t = apq / h;                  // theta squared overflows (or is NaN): the small-angle limit
                         }
-                        const T c = T(1) / rg_sqrt<T>(t * t + T(1));
+                        const T c = T(1) / sqrt_t<T>(t * t + T(1));
                         const T s = t * c;
                         const T tau = s / (T(1) + c);
                         const T hh = t * apq;
@@ -219,7 +211,7 @@ __device__ __forceinline__ T rg_frangi(const T *lam, T a2, T b2, T g2)
         const T l1 = lam[0], l2 = lam[1], l3 = lam[2];
         const T qa = l2 / rg_nonzero<T>(l3);
         const T ra = qa * qa;
-        const T raw = rg_sqrt<T>(rg_abs<T>(l2 * l3));
+        const T raw = sqrt_t<T>(rg_abs<T>(l2 * l3));
         const T qb = l1 / rg_nonzero<T>(raw);
         const T rb = qb * qb;
         const T rg = (l1 * l1 + l2 * l2) + l3 * l3;
@@ -234,7 +226,7 @@ __device__ __forceinline__ T rg_sato(const T *lam)
 {
     static_assert(N == 2 || N == 3, "sato is defined for 2-D and 3-D");
     if constexpr (N == 2) return lam[1] > T(0) ? rg_abs<T>(lam[1]) : T(0);
-    else return lam[2] > T(0) ? rg_sqrt<T>(rg_abs<T>(lam[1] * lam[2])) : T(0);
+    else return lam[2] > T(0) ? sqrt_t<T>(rg_abs<T>(lam[1] * lam[2])) : T(0);
 }
 
 // meijering: lam ordered by |.|.  ridges.py:262-278 as written: element i of `auxiliary` is the sum over j of
@@ -317,16 +309,11 @@ __device__ __forceinline__ unsigned long long rg_finish(const T *e, const RgOut 
 }
 
 // ------------------------------------------------------------------ tile kernels (2-D and 3-D)
-struct RgTile {
-    int n[3];                // nz, ny, nx (nz = 1 for images)
-    int t[3];                // tile planes, rows, columns (columns: a power of two, at most 64)
-    int nt[3];               // tiles along z, y, x
-};
-
+// g: the tiles (BoxDims, nz = 1 for images), their columns g.t[2] a power of two, at most 64
 // WHAT: 0 = write the elements (XY: order "xy", else "rc"), 1 = go on to eigenvalues and response
 template <typename T, int ND, int WHAT, bool XY>
 __global__ void __launch_bounds__(kRgNT)
-ridge_tile_kernel(const T *__restrict__ G, T *__restrict__ elems, const RgTile g, const RgOut o)
+ridge_tile_kernel(const T *__restrict__ G, T *__restrict__ elems, const BoxDims g, const RgOut o)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char rg_lds[];
     T *S = reinterpret_cast<T *>(rg_lds);
@@ -405,21 +392,14 @@ ridge_tile_kernel(const T *__restrict__ G, T *__restrict__ elems, const RgTile g
 }
 
 // ------------------------------------------------------------------ per-voxel kernels (any rank)
-struct RgGeom {
-    int nd;
-    int64_t total;
-    int64_t shape[MI_MAX_NDIM];
-    int64_t stride[MI_MAX_NDIM];       // elements
-};
-
 template <typename T>
 __global__ void __launch_bounds__(kRgNT)
-hessian_generic_kernel(const T *__restrict__ G, T *__restrict__ elems, const RgGeom g, int xy)
+hessian_generic_kernel(const T *__restrict__ G, T *__restrict__ elems, const VoxelGeom<MI_MAX_NDIM> g, int xy)
 {
     for (int64_t i = (int64_t)blockIdx.x * kRgNT + threadIdx.x; i < g.total; i += (int64_t)gridDim.x * kRgNT) {
         int64_t c[MI_MAX_NDIM], n[MI_MAX_NDIM];
         int64_t r = i;
-        for (int a = MI_MAX_NDIM - 1; a >= 0; a--) {
+        for (int a = MI_MAX_NDIM - 1; a >= 0; a--) {         // voxel_coords and the lengths in one rolled loop
             c[a] = 0; n[a] = 1;
             if (a < g.nd) {
                 const int64_t qq = r / g.shape[a];
@@ -484,28 +464,13 @@ fill_nonpositive_kernel(double *__restrict__ a, int64_t total, double value)
 // test / tuning hook: tile rows, tile planes (0 = the planner's), every call on the per-voxel kernels
 static Knob g_rg_ty{0}, g_rg_tz{0}, g_rg_generic{0};
 
-static void rg_geom(const mi_array *a, RgGeom *g)
-{
-    memset(g, 0, sizeof(*g));
-    g->nd = a->ndim;
-    int64_t st = 1;
-    for (int d = a->ndim - 1; d >= 0; d--) {
-        g->shape[d] = a->shape[d];
-        g->stride[d] = st;
-        st *= a->shape[d];
-    }
-    g->total = st;
-}
-
 static int rg_grid(int64_t total)
 {
-    dim3 grid;
-    grid_for(total, kRgNT, &grid);
-    return (int)grid.x;
+    return capped_grid(total, kRgNT, 8192);
 }
 
 // the tile plan of a 2-D / 3-D array; false: not a shape of the tile kernels
-static bool rg_plan(const mi_array *a, RgTile *p, size_t *lds)
+static bool rg_plan(const mi_array *a, BoxDims *p, size_t *lds)
 {
     if (a->ndim != 2 && a->ndim != 3) return false;
     const bool vol = a->ndim == 3;
@@ -533,7 +498,7 @@ static bool rg_plan(const mi_array *a, RgTile *p, size_t *lds)
 }
 
 template <typename T, int ND, int WHAT, bool XY>
-static int launch_rg_tile(const mi_array *G, void *elems, const RgTile &p, size_t lds, const RgOut &o, hipStream_t s)
+static int launch_rg_tile(const mi_array *G, void *elems, const BoxDims &p, size_t lds, const RgOut &o, hipStream_t s)
 {
     const int grid = p.nt[0] * p.nt[1] * p.nt[2];
     hipLaunchKernelGGL((ridge_tile_kernel<T, ND, WHAT, XY>), dim3((unsigned)grid), dim3(kRgNT), lds, s, (const T *)G->data, (T *)elems, p, o);
@@ -572,7 +537,7 @@ static int rg_check_2d(const mi_array *a, int64_t rows, int64_t total, int dt, c
 
 static int hessian_elements(const mi_array *G, void *elems, int xy, bool allow_tile, hipStream_t s)
 {
-    RgTile p;
+    BoxDims p;
     size_t lds = 0;
     const bool f32 = G->dtype == MI_F32;
     if (allow_tile && rg_plan(G, &p, &lds)) {
@@ -584,8 +549,8 @@ static int hessian_elements(const mi_array *G, void *elems, int xy, bool allow_t
         return f32 ? RG_H(float) : RG_H(double);
 #undef RG_H
     }
-    RgGeom g;
-    rg_geom(G, &g);
+    VoxelGeom<MI_MAX_NDIM> g;
+    voxel_geom(G, &g);
     const int grid = rg_grid(g.total);
     if (f32) hipLaunchKernelGGL(hessian_generic_kernel<float>, dim3(grid), dim3(kRgNT), 0, s, (const float *)G->data, (float *)elems, g, xy);
     else hipLaunchKernelGGL(hessian_generic_kernel<double>, dim3(grid), dim3(kRgNT), 0, s, (const double *)G->data, (double *)elems, g, xy);
@@ -705,7 +670,7 @@ extern "C" int mi_ridge_scale(const mi_array *g, const mi_array *out, int kind, 
         o.slot = (unsigned long long *)work_dev;
     }
     hipStream_t s = resolve_stream(stream);
-    RgTile p;
+    BoxDims p;
     size_t lds = 0;
     const bool f32 = g->dtype == MI_F32;
     if (!g_rg_generic && rg_plan(g, &p, &lds)) {

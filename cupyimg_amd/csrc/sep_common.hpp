@@ -6,10 +6,6 @@ namespace mi {
 
 constexpr int kMaxTaps = 9;
 
-// remembers (per host thread) which kernel a separable-filter call dispatched: mi_debug_last_kernel (bench.py names
-// the kernel it timed from this, not from a literal)
-void note_kernel(const char *fmt, ...);
-
 // Dry run (per host thread): separable3d_impl and run_sep3d_long walk their whole decision tree and return MI_OK where
 // they would launch, MI_ERR_UNSUPPORTED / MI_ERR_INVALID_ARG where they would refuse -- nothing is queued.  A request
 // that names plane ranges is treated as a partial one even when the ranges happen to cover the array, so that the

@@ -33,8 +33,6 @@
 #include "common.hpp"
 
 namespace mi {
-void note_kernel(const char *fmt, ...);        // runtime.hip
-
 static Knob g_spline_fast{1};      // test hook: 0 = never these kernels, 1 = by the rules below, 2 = also for few lines
 }  // namespace mi
 extern "C" int mi_debug_set_spline_fast(int k) { mi::g_spline_fast = k; return MI_OK; }

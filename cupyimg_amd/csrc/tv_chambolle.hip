@@ -26,11 +26,9 @@
 // tv_generic_kernel: the same arithmetic with one thread per voxel straight from global memory, ranks 1 .. MI_MAX_NDIM.
 // tv_energy_kernel: one workgroup adds the partials in a fixed order, forms E_i and applies the stopping rule in the state block.
 // tv_output_kernel: out = image + d(p).
-#include "common.hpp"
-#include <algorithm>
+#include "skimage_common.hpp"
 
 namespace mi {
-void note_kernel(const char *fmt, ...);      // separable3d.hip: which kernel a call dispatched (mi_debug_last_kernel)
 
 constexpr int kTvNT = 256;
 
@@ -71,13 +69,6 @@ __device__ __forceinline__ void tv_block_partials(double sdd, double snorm, doub
         part[2 * (int64_t)blockIdx.x] = red[0][0];
         part[2 * (int64_t)blockIdx.x + 1] = red[1][0];
     }
-}
-
-template <typename T>
-__device__ __forceinline__ T tv_sqrt(T v)
-{
-    if constexpr (std::is_same<T, float>::value) return __builtin_sqrtf(v);
-    else return __builtin_sqrt(v);
 }
 
 // VOL: axis 0 is an axis of the array (p has 3 components); false: an image as one plane (2 components, no p_0)
@@ -153,7 +144,7 @@ tv_fused_kernel(const T *__restrict__ img, const T *__restrict__ pin, T *__restr
                     T n2;
                     if (VOL) n2 = (g0 * g0 + g1 * g1) + g2 * g2;
                     else n2 = g1 * g1 + g2 * g2;
-                    const T nrm = tv_sqrt<T>(n2);
+                    const T nrm = sqrt_t<T>(n2);
                     snorm += (double)nrm;
                     const T den = nrm * tw + T(1);
                     const int64_t q = (int64_t)zu * plane + gi;
@@ -194,20 +185,13 @@ tv_fused_kernel(const T *__restrict__ img, const T *__restrict__ pin, T *__restr
     tv_block_partials(sdd, snorm, part);
 }
 
-struct TvGeom {
-    int nd;
-    int64_t total;
-    int64_t shape[MI_MAX_NDIM];
-    int64_t stride[MI_MAX_NDIM];       // elements
-};
-
 // The per-voxel kernels are built for the ranks 1 .. 4 (ND = the rank: trip counts known to the compiler) and once for
 // 5 .. MI_MAX_NDIM (ND = MI_MAX_NDIM, axes beyond g.nd skipped at run time).
 #define TV_AXIS(a) (ND != MI_MAX_NDIM || (a) < g.nd)
 
 // d(q) for the voxel at linear index i with coordinates c
 template <typename T, int ND>
-__device__ __forceinline__ T tv_d_at(const T *__restrict__ p, const TvGeom &g, int64_t i, const int64_t *c)
+__device__ __forceinline__ T tv_d_at(const T *__restrict__ p, const VoxelGeom<MI_MAX_NDIM> &g, int64_t i, const int64_t *c)
 {
     T s = p[i];
 #pragma unroll
@@ -220,31 +204,16 @@ __device__ __forceinline__ T tv_d_at(const T *__restrict__ p, const TvGeom &g, i
     return d;
 }
 
-template <int ND>
-__device__ __forceinline__ void tv_coords(const TvGeom &g, int64_t i, int64_t *c)
-{
-    int64_t r = i;
-#pragma unroll
-    for (int a = ND - 1; a >= 0; a--) {
-        c[a] = 0;
-        if (TV_AXIS(a)) {
-            const int64_t q = r / g.shape[a];
-            c[a] = r - q * g.shape[a];
-            r = q;
-        }
-    }
-}
-
 template <typename T, int ND>
 __global__ void __launch_bounds__(kTvNT)
-tv_generic_kernel(const T *__restrict__ img, const T *__restrict__ pin, T *__restrict__ pout, const TvGeom g, const T tau, const T tw,
+tv_generic_kernel(const T *__restrict__ img, const T *__restrict__ pin, T *__restrict__ pout, const VoxelGeom<MI_MAX_NDIM> g, const T tau, const T tw,
                   double *__restrict__ part, const TvState *__restrict__ state)
 {
     if (state->stopped) return;
     double sdd = 0.0, snorm = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * kTvNT + threadIdx.x; i < g.total; i += (int64_t)gridDim.x * kTvNT) {
         int64_t c[ND];
-        tv_coords<ND>(g, i, c);
+        voxel_coords<ND, ND == MI_MAX_NDIM>(g, i, c);
         const T d = tv_d_at<T, ND>(pin, g, i, c);
         const T o = img[i] + d;
         sdd += (double)(d * d);
@@ -263,7 +232,7 @@ tv_generic_kernel(const T *__restrict__ img, const T *__restrict__ pin, T *__res
                 n2 = a == 0 ? gr[a] * gr[a] : n2 + gr[a] * gr[a];
             }
         }
-        const T nrm = tv_sqrt<T>(n2);
+        const T nrm = sqrt_t<T>(n2);
         snorm += (double)nrm;
         const T den = nrm * tw + T(1);
 #pragma unroll
@@ -275,11 +244,11 @@ tv_generic_kernel(const T *__restrict__ img, const T *__restrict__ pin, T *__res
 
 template <typename T, int ND>
 __global__ void __launch_bounds__(kTvNT)
-tv_output_kernel(const T *__restrict__ img, const T *__restrict__ p, T *__restrict__ out, const TvGeom g)
+tv_output_kernel(const T *__restrict__ img, const T *__restrict__ p, T *__restrict__ out, const VoxelGeom<MI_MAX_NDIM> g)
 {
     for (int64_t i = (int64_t)blockIdx.x * kTvNT + threadIdx.x; i < g.total; i += (int64_t)gridDim.x * kTvNT) {
         int64_t c[ND];
-        tv_coords<ND>(g, i, c);
+        voxel_coords<ND, ND == MI_MAX_NDIM>(g, i, c);
         out[i] = img[i] + tv_d_at<T, ND>(p, g, i, c);
     }
 }
@@ -327,24 +296,6 @@ tv_energy_kernel(const double *__restrict__ part, int npart, double weight, doub
 static Knob g_tv_ty{0}, g_tv_zc{0}, g_tv_narrow{0}, g_tv_generic{0};
 
 constexpr int kTvGenericMaxGrid = 2048;
-
-static void tv_geom(const mi_array *image, TvGeom *g)
-{
-    memset(g, 0, sizeof(*g));
-    g->nd = image->ndim;
-    int64_t st = 1;
-    for (int d = image->ndim - 1; d >= 0; d--) {
-        g->shape[d] = image->shape[d];
-        g->stride[d] = st;
-        st *= image->shape[d];
-    }
-    g->total = st;
-}
-
-static int tv_grid(int64_t total)
-{
-    return (int)std::min<int64_t>((total + kTvNT - 1) / kTvNT, kTvGenericMaxGrid);
-}
 
 template <typename T, bool VOL, int TX>
 static int launch_tv_fused(const mi_array *image, const mi_array *p_in, const mi_array *p_out, const TvParams &p, size_t lds, double tau,
@@ -472,9 +423,9 @@ extern "C" int mi_tv_chambolle_step(const mi_array *image, const mi_array *p_in,
     rc = MI_ERR_UNSUPPORTED;
     if (!g_tv_generic && (image->ndim == 2 || image->ndim == 3)) rc = tv_fused(image, p_in, p_out, tau, weight, part, state, &npart, s);
     if (rc == MI_ERR_UNSUPPORTED) {
-        TvGeom g;
-        tv_geom(image, &g);
-        npart = tv_grid(total);
+        VoxelGeom<MI_MAX_NDIM> g;
+        voxel_geom(image, &g);
+        npart = capped_grid(total, kTvNT, kTvGenericMaxGrid);          // total >= 1 here
 #define TV_GEN(T, ND)                                                                                                         \
     hipLaunchKernelGGL((tv_generic_kernel<T, ND>), dim3(npart), dim3(kTvNT), 0, s, (const T *)image->data, (const T *)p_in->data, \
                        (T *)p_out->data, g, (T)tau, (T)(tau / weight), part, (const TvState *)state)
@@ -501,9 +452,9 @@ extern "C" int mi_tv_chambolle_output(const mi_array *image, const mi_array *p, 
     const int64_t total = numel(image);
     if (total == 0) return MI_OK;
     hipStream_t s = resolve_stream(stream);
-    TvGeom g;
-    tv_geom(image, &g);
-    const int grid = (int)std::min<int64_t>((total + kTvNT - 1) / kTvNT, 65536);
+    VoxelGeom<MI_MAX_NDIM> g;
+    voxel_geom(image, &g);
+    const int grid = capped_grid(total, kTvNT, 65536);
 #define TV_OUT(T, ND)                                                                                                         \
     hipLaunchKernelGGL((tv_output_kernel<T, ND>), dim3(grid), dim3(kTvNT), 0, s, (const T *)image->data, (const T *)p->data,      \
                        (T *)out->data, g)

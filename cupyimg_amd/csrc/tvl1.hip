@@ -36,50 +36,22 @@
 // memory (u^1 and p^1 in a scratch array), ranks 2 .. 4; the forced comparison route for 2-D and 3-D.
 // tvl1_diff_kernel / tvl1_diff_final_kernel: sum (a - b)^2, the difference and its square in T, the sum in double from
 // per-workgroup partials in an order fixed by the size: no floating-point atomics.
-#include "common.hpp"
-#include <algorithm>
+#include "skimage_common.hpp"
 
 namespace mi {
-void note_kernel(const char *fmt, ...);      // separable3d.hip: which kernel a call dispatched (mi_debug_last_kernel)
 
 constexpr int kFlNT = 256;
 constexpr int kFlMaxNd = 4;
 constexpr int kFlMaxGrid = 4096;
 constexpr int kFlDiffGrid = 1024;
 
-template <typename T>
-__device__ __forceinline__ T fl_sqrt(T v)
-{
-    if constexpr (std::is_same<T, float>::value) return __builtin_sqrtf(v);
-    else return __builtin_sqrt(v);
-}
-
-struct FlGeom {
-    int nd;
-    int64_t total;
-    int64_t shape[kFlMaxNd];
-    int64_t stride[kFlMaxNd];       // elements
-};
-
-template <int ND>
-__device__ __forceinline__ void fl_coords(const FlGeom &g, int64_t i, int64_t *c)
-{
-    int64_t r = i;
-#pragma unroll
-    for (int a = ND - 1; a >= 0; a--) {
-        const int64_t q = r / g.shape[a];
-        c[a] = r - q * g.shape[a];
-        r = q;
-    }
-}
-
 template <typename T, int ND>
 __global__ void __launch_bounds__(kFlNT)
-tvl1_coords_kernel(const T *__restrict__ flow, T *__restrict__ out, const FlGeom g)
+tvl1_coords_kernel(const T *__restrict__ flow, T *__restrict__ out, const VoxelGeom<kFlMaxNd> g)
 {
     for (int64_t i = (int64_t)blockIdx.x * kFlNT + threadIdx.x; i < g.total; i += (int64_t)gridDim.x * kFlNT) {
         int64_t c[ND];
-        fl_coords<ND>(g, i, c);
+        voxel_coords<ND, false>(g, i, c);
 #pragma unroll
         for (int a = 0; a < ND; a++) out[a * g.total + i] = (T)c[a] + flow[a * g.total + i];
     }
@@ -88,11 +60,11 @@ tvl1_coords_kernel(const T *__restrict__ flow, T *__restrict__ out, const FlGeom
 template <typename T, int ND>
 __global__ void __launch_bounds__(kFlNT)
 tvl1_prepare_kernel(const T *__restrict__ w, const T *__restrict__ ref, const T *__restrict__ flow, T *__restrict__ grad,
-                    T *__restrict__ ni, T *__restrict__ rho0, const FlGeom g)
+                    T *__restrict__ ni, T *__restrict__ rho0, const VoxelGeom<kFlMaxNd> g)
 {
     for (int64_t i = (int64_t)blockIdx.x * kFlNT + threadIdx.x; i < g.total; i += (int64_t)gridDim.x * kFlNT) {
         int64_t c[ND];
-        fl_coords<ND>(g, i, c);
+        voxel_coords<ND, false>(g, i, c);
         const T wi = w[i];
         T s = T(0), dot = T(0);
 #pragma unroll
@@ -143,13 +115,13 @@ tvl1_data_kernel(const T *__restrict__ grad, const T *__restrict__ ni, const T *
 // p_out[c] = one dual step of p_in[c] against u[c]; index over (component, voxel)
 template <typename T, int ND>
 __global__ void __launch_bounds__(kFlNT)
-tvl1_step_p_kernel(const T *__restrict__ u, const T *__restrict__ pin, T *__restrict__ pout, const FlGeom g, const T dt, const T f1)
+tvl1_step_p_kernel(const T *__restrict__ u, const T *__restrict__ pin, T *__restrict__ pout, const VoxelGeom<kFlMaxNd> g, const T dt, const T f1)
 {
     const int64_t all = g.total * ND;
     for (int64_t j = (int64_t)blockIdx.x * kFlNT + threadIdx.x; j < all; j += (int64_t)gridDim.x * kFlNT) {
         const int64_t cmp = j / g.total, i = j - cmp * g.total;
         int64_t c[ND];
-        fl_coords<ND>(g, i, c);
+        voxel_coords<ND, false>(g, i, c);
         const T *uc = u + cmp * g.total;
         const T u0 = uc[i];
         T gr[ND];
@@ -159,7 +131,7 @@ tvl1_step_p_kernel(const T *__restrict__ u, const T *__restrict__ pin, T *__rest
             gr[a] = c[a] < g.shape[a] - 1 ? uc[i + g.stride[a]] - u0 : T(0);
             s = a == 0 ? gr[a] * gr[a] : s + gr[a] * gr[a];
         }
-        T norm = fl_sqrt<T>(s);
+        T norm = sqrt_t<T>(s);
         norm = norm * f1;
         norm = norm + T(1);
 #pragma unroll
@@ -173,13 +145,13 @@ tvl1_step_p_kernel(const T *__restrict__ u, const T *__restrict__ pin, T *__rest
 // out[c] = v[c] - div p[c]
 template <typename T, int ND>
 __global__ void __launch_bounds__(kFlNT)
-tvl1_step_u_kernel(const T *__restrict__ v, const T *__restrict__ p, T *__restrict__ out, const FlGeom g)
+tvl1_step_u_kernel(const T *__restrict__ v, const T *__restrict__ p, T *__restrict__ out, const VoxelGeom<kFlMaxNd> g)
 {
     const int64_t all = g.total * ND;
     for (int64_t j = (int64_t)blockIdx.x * kFlNT + threadIdx.x; j < all; j += (int64_t)gridDim.x * kFlNT) {
         const int64_t cmp = j / g.total, i = j - cmp * g.total;
         int64_t c[ND];
-        fl_coords<ND>(g, i, c);
+        voxel_coords<ND, false>(g, i, c);
         const T *pc = p + cmp * ND * g.total;
         T s = pc[i];
 #pragma unroll
@@ -298,7 +270,7 @@ tvl1_reg_fused_kernel(const T *__restrict__ vin, const T *__restrict__ pin, T *_
                     T n2;
                     if (VOL) n2 = (gz * gz + gy * gy) + gx * gx;
                     else n2 = gy * gy + gx * gx;
-                    T norm = fl_sqrt<T>(n2);
+                    T norm = sqrt_t<T>(n2);
                     norm = norm * f1;
                     norm = norm + T(1);
                     if (VOL) Pb[l] = (Pb[l] - dt * gz) / norm;
@@ -347,7 +319,7 @@ tvl1_reg_fused_kernel(const T *__restrict__ vin, const T *__restrict__ pin, T *_
                     T n2;
                     if (VOL) n2 = (gz * gz + gy * gy) + gx * gx;
                     else n2 = gy * gy + gx * gx;
-                    T norm = fl_sqrt<T>(n2);
+                    T norm = sqrt_t<T>(n2);
                     norm = norm * f1;
                     norm = norm + T(1);
                     if (VOL) Pb[l] = (Pb[l] - dt * gz) / norm;
@@ -427,7 +399,7 @@ static Knob g_fl_small{0}, g_fl_generic{0};
 
 static int fl_grid(int64_t n)
 {
-    return (int)std::min<int64_t>((n + kFlNT - 1) / kFlNT, kFlMaxGrid);
+    return capped_grid(n, kFlNT, kFlMaxGrid);
 }
 
 // image: (n_0, ...), rank 2 .. 4, float32 / float64, C-contiguous, every axis at least 2 long
@@ -477,19 +449,6 @@ static int fl_image_of(const mi_array *flow, mi_array *image)
         st *= image->shape[d];
     }
     return fl_check_image(image, "flow");
-}
-
-static void fl_geom(const mi_array *image, FlGeom *g)
-{
-    memset(g, 0, sizeof(*g));
-    g->nd = image->ndim;
-    int64_t st = 1;
-    for (int d = image->ndim - 1; d >= 0; d--) {
-        g->shape[d] = image->shape[d];
-        g->stride[d] = st;
-        st *= image->shape[d];
-    }
-    g->total = st;
 }
 
 // GO(T, ND) for the dtype and rank
@@ -594,8 +553,8 @@ extern "C" int mi_tvl1_coords(const mi_array *flow, const mi_array *coords, mi_s
     mi_array image;
     if ((rc = fl_image_of(flow, &image)) || (rc = fl_check_field(coords, 1, image.ndim, image.shape, image.dtype, "coords"))) return rc;
     MI_REQUIRE(coords->data != flow->data, MI_ERR_INVALID_ARG, "coords may not be the flow");
-    FlGeom g;
-    fl_geom(&image, &g);
+    VoxelGeom<kFlMaxNd> g;
+    voxel_geom(&image, &g);
     hipStream_t s = resolve_stream(stream);
     const int grid = fl_grid(g.total);
 #define FL_COORDS(T, ND) hipLaunchKernelGGL((tvl1_coords_kernel<T, ND>), dim3(grid), dim3(kFlNT), 0, s, (const T *)flow->data, (T *)coords->data, g)
@@ -617,8 +576,8 @@ extern "C" int mi_tvl1_prepare(const mi_array *warped, const mi_array *reference
         return rc;
     MI_REQUIRE(grad->data != warped->data && grad->data != flow->data && ni->data != warped->data && rho0->data != warped->data &&
                rho0->data != reference->data, MI_ERR_INVALID_ARG, "tvl1_prepare: outputs may not be inputs");
-    FlGeom g;
-    fl_geom(warped, &g);
+    VoxelGeom<kFlMaxNd> g;
+    voxel_geom(warped, &g);
     hipStream_t s = resolve_stream(stream);
     const int grid = fl_grid(g.total);
 #define FL_PREP(T, ND)                                                                                                        \
@@ -685,8 +644,8 @@ extern "C" int mi_tvl1_reg(const mi_array *flow_aux, const mi_array *proj_in, co
     }
     if (rc != MI_ERR_UNSUPPORTED) return rc;
     MI_REQUIRE(scratch_dev, MI_ERR_INVALID_ARG, "tvl1_reg: the per-voxel route needs the scratch block (mi_tvl1_scratch_size)");
-    FlGeom g;
-    fl_geom(&image, &g);
+    VoxelGeom<kFlMaxNd> g;
+    voxel_geom(&image, &g);
     const int grid = fl_grid(g.total * nd);
 #define FL_GEN(T, ND)                                                                                                         \
     do {                                                                                                                      \
@@ -719,7 +678,7 @@ extern "C" int mi_tvl1_diff_sum(const mi_array *a, const mi_array *b, void *work
     const int64_t n = numel(a);
     hipStream_t s = resolve_stream(stream);
     double *result = (double *)work_dev, *part = result + 8;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + kFlNT - 1) / kFlNT, kFlDiffGrid));
+    const int grid = capped_grid(n, kFlNT, kFlDiffGrid);
     if (a->dtype == MI_F32)
         hipLaunchKernelGGL((tvl1_diff_kernel<float>), dim3(grid), dim3(kFlNT), 0, s, (const float *)a->data, (const float *)b->data, n, part);
     else
