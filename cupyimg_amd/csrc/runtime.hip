@@ -110,6 +110,9 @@ struct Pool {
 };
 static Pool g_pool;
 
+// test hook (mi_debug_set_pool_fill): 0 = off, 0x100 | byte = every block handed out is first filled with `byte`
+static Knob g_pool_fill(0);
+
 static size_t round_size(size_t n)
 {
     if (n == 0) n = 1;
@@ -167,6 +170,10 @@ int pool_alloc(void **p, size_t n, hipStream_t stream)
     }
     g_pool.live[*p] = {dev, sz, stream};
     g_pool.in_use += sz;
+    // Poisoned blocks for the tests: the whole rounded block, slack included, fresh or recycled.  The memset is queued
+    // on the stream the block is handed out for, and by the contract above the block is only used by work on that
+    // stream, so it is ordered ahead of every use without an event or a synchronisation.  Off: this one relaxed load.
+    if (const int fill = g_pool_fill) MI_HIP(hipMemsetAsync(*p, fill & 0xff, sz, stream));
     return MI_OK;
 }
 
@@ -258,6 +265,13 @@ int mi_debug_pool_probe(size_t nbytes, mi_stream stream, void **block)
     if (rc != MI_OK) return rc;
     if (block) *block = p;
     return pool_free(p);
+}
+
+// test hook (not part of the C-ABI): on != 0: pool_alloc fills every block it hands out with `byte` (0 .. 255)
+int mi_debug_set_pool_fill(int on, int byte)
+{
+    g_pool_fill = on ? (0x100 | (byte & 0xff)) : 0;
+    return MI_OK;
 }
 
 int mi_pool_trim(void)

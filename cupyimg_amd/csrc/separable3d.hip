@@ -941,7 +941,7 @@ extern "C" int mi_debug_set_sep3d_cfg(int cfg) { g_sep3d_cfg = cfg; return MI_OK
 extern "C" int mi_debug_set_sep3d_zchunks(int n) { g_sep3d_zchunks = n; return MI_OK; }
 extern "C" int mi_debug_set_sep3d_dbg(int f) { g_sep3d_dbg = f; return MI_OK; }
 extern "C" int mi_debug_set_sep3d_kernel(int k) { g_sep3d_kernel = k; return MI_OK; }
-static mi::Knob g_sep3d_box{0};       // 0 = auto (running-sum box kernel where it applies), 1 = off
+static mi::Knob g_sep3d_box{0};       // read nowhere: no running-sum box kernel exists, uniform_filter takes the kernels of its tap count
 extern "C" int mi_debug_set_sep3d_ragged(int k) { g_sep3d_ragged = k; return MI_OK; }
 extern "C" int mi_debug_set_sep3d_box(int k) { g_sep3d_box = k; return MI_OK; }
 extern "C" int mi_debug_last_kernel(char *buf, size_t n)

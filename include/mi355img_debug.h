@@ -23,7 +23,7 @@ int mi_debug_set_sep3d_kernel(int k);         /* 1 = always the general (ws) ker
 int mi_debug_set_sep3d_zrev(int on);          /* 0 = every z chunk streams upwards */
 int mi_debug_set_sep3d_image2d(int on);       /* 0 = images take the tiled volume kernel */
 int mi_debug_set_sep3d_long(int k);           /* 0 auto (9..17 taps, and 3..7 taps on large volumes with full tiles), 1 never the long kernel, 2 long kernel for all of 3..17 taps */
-int mi_debug_set_sep3d_box(int k);            /* 0 auto, 1 never the running-sum box kernel */
+int mi_debug_set_sep3d_box(int k);            /* no effect: the value is stored and read nowhere (no running-sum box kernel exists; kept for the ABI) */
 int mi_debug_set_sep3d_ragged(int k);         /* r5: 1 (default) the 3 / 5 / 7-tap kernel takes rows that are not a multiple of 4 floats, 0 refuse them (r6: the switch also covers the 9 .. 17-tap LDS-DMA kernel's ragged build) */
 int mi_debug_set_median27(int k);             /* r5: 1 (default) 3 x 3 x 3 medians of volumes on the shared-sort streaming kernel, 0 the per-voxel network */
 int mi_debug_set_long_const0(int k);          /* r5: 1 (default) constant mode with cval == 0 on the r3 long kernel, 0 the r2 kernel */
@@ -49,6 +49,9 @@ int mi_debug_fill_synthetic_f32(float *out, int64_t n, uint64_t first_index, uin
 
 /* pool test hook (csrc/runtime.hip): allocate `nbytes` for work on `stream`, report the block, free it again */
 int mi_debug_pool_probe(size_t nbytes, mi_stream stream, void **block);
+/* pool test hook: on != 0: every block the pool hands out (fresh or recycled, outputs and scratch alike) is first filled
+ * with `byte` over its whole rounded size, by a memset queued on the stream it is handed out for; 0 (default): untouched */
+int mi_debug_set_pool_fill(int on, int byte);
 
 /* ---- other kernel families */
 int mi_debug_generation(void);                /* advances with every mi_debug_set_* call: part of the keys of host-side refusal caches */
