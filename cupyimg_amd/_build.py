@@ -85,6 +85,7 @@ SOURCES = [
     ("tvl1.hip", ["-ffp-contract=off"]),
     ("edges.hip", ["-ffp-contract=off"]),
     ("corners.hip", ["-ffp-contract=off"]),
+    ("select.hip", []),
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function",
           "-I" + os.path.join(os.path.dirname(HERE), "include")]

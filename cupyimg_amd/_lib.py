@@ -165,6 +165,16 @@ SIGNATURES = {
     "mi_threshold_masks":[_arr, _arr, _arr, _d, _d, _arr, _arr, _vp],
     "mi_structure_products": [_arr, _arr, _i, _i, _i, _d, _vp],
     "mi_corner_response": [_arr, _arr, _arr, _i, _d, _d, _vp],
+    "mi_select_work_bytes": [ctypes.c_int64, _i64p],
+    "mi_select_count": [_arr, _arr, _i64p, _vp],
+    "mi_select_write": [_arr, _arr, _arr, _i, _vp],
+    "mi_take": [_arr, _arr, _arr, ctypes.c_int64, _vp, _vp],
+    "mi_argsort": [_arr, _arr, _arr, _i, _vp],
+    "mi_peak_count": [_arr, _arr, _d, _i64p, _arr, _i64p, _i64p, _vp],
+    "mi_peak_write": [_arr, _arr, _d, _i64p, _arr, _arr, _arr, _vp],
+    "mi_spacing_init": [_arr, _arr, _arr, _ip, _vp],
+    "mi_spacing_rounds": [_arr, _arr, _arr, ctypes.c_int64, _i, _i, _i, _ip, _vp],
+    "mi_scatter_true": [_arr, _arr, _vp],
     "mi_map_coordinates": [_arr, _arr, _arr, _i, _i, _d, _vp],
     "mi_affine_transform": [_arr, _arr, _dp, _i, _i, _d, _vp],
     "mi_spline_pad": [_arr, _arr, _i, _i, _d, _vp],

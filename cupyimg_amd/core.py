@@ -596,6 +596,139 @@ def arrays_differ(a, b):
     return bool(flag.get()[0])
 
 
+# --------------------------------------------------------------------- selection, gather, sorting (csrc/select.hip)
+_SELECT_MAX = 2 ** 31 - 1
+
+
+def _select_input(a):
+    """C-contiguous device array within the family's limits (a strided view is compacted first, as the reductions do)"""
+    a = asarray(a)
+    if a.dtype == np.float16:
+        raise TypeError("float16 arrays are storage only: convert with astype(float32) around this call")
+    if a.size > _SELECT_MAX:
+        raise ValueError("selection and sorting take at most 2**31 - 1 elements")
+    return ascontiguousarray(a)
+
+
+def _select_check(rc):
+    try:
+        _lib.check(rc, ValueError)
+    except _lib.Unsupported as exc:
+        raise ValueError(str(exc))
+
+
+def _select_count(a):
+    """(K, work): the count call of a compaction; `work` keeps the scanned per-tile counts for the write call"""
+    lib = _lib.load()
+    nbytes = ctypes.c_int64()
+    _select_check(lib.mi_select_work_bytes(a.size, ctypes.byref(nbytes)))
+    work = ndarray((nbytes.value,), np.uint8)
+    total = ctypes.c_int64()
+    ad, wd = a._desc(), work._desc()
+    _select_check(lib.mi_select_count(ctypes.byref(ad), ctypes.byref(wd), ctypes.byref(total), None))
+    return total.value, work
+
+
+def _select_write(a, work, out, layout):
+    ad, wd, od = a._desc(), work._desc(), out._desc()
+    _select_check(_lib.load().mi_select_write(ctypes.byref(ad), ctypes.byref(wd), ctypes.byref(od), layout, None))
+    return out
+
+
+def count_nonzero(a):
+    """Number of nonzero elements as a Python int (NaN counts, -0.0 does not): the count launch, the scan, one 8-byte read."""
+    a = _select_input(a)
+    return _select_count(a)[0] if a.size else 0
+
+
+def flatnonzero(a):
+    """Flat indices of the nonzero elements, int64, in raster order (numpy.flatnonzero)."""
+    a = _select_input(a)
+    if not a.size:
+        return ndarray((0,), np.int64)
+    k, work = _select_count(a)
+    return _select_write(a, work, ndarray((k,), np.int64), 0)
+
+
+def argwhere(a):
+    """(K, ndim) int64 indices of the nonzero elements in raster order (numpy.argwhere), unravelled in the write kernel."""
+    a = _select_input(a)
+    if not a.size or not a.ndim:
+        k = count_nonzero(a) if a.size else 0
+        return ndarray((k, a.ndim), np.int64)
+    k, work = _select_count(a)
+    return _select_write(a, work, ndarray((k, a.ndim), np.int64), 1)
+
+
+def nonzero(a):
+    """Tuple of ndim int64 arrays, the indices of the nonzero elements along each axis (numpy.nonzero); the arrays are the
+    rows of one (ndim, K) block."""
+    a = _select_input(a)
+    if not a.ndim:
+        raise ValueError("nonzero of a 0-d array is not defined; use flatnonzero")
+    if not a.size:
+        return tuple(ndarray((0,), np.int64) for _ in range(a.ndim))
+    k, work = _select_count(a)
+    block = _select_write(a, work, ndarray((a.ndim, k), np.int64), 2)
+    return tuple(block[d] for d in range(a.ndim))
+
+
+def _take_rows(a, indices, inner):
+    """out[k, :] = a.reshape(-1, inner)[indices[k], :]; IndexError when an index is out of range (checked on the device)"""
+    a = _select_input(a)
+    indices = ascontiguousarray(asarray(indices))
+    if indices.dtype != np.int64:
+        if indices.dtype.kind not in "iu":
+            raise IndexError("indices must be integers")
+        indices = indices.astype(np.int64)
+    out = ndarray(tuple(indices.shape) + (inner,), a.dtype)
+    if not indices.size:
+        return out
+    if not a.size:
+        raise IndexError("cannot take from an empty array")
+    flag = zeros((1,), np.int32)
+    ad, idd, od = a._desc(), indices._desc(), out._desc()
+    _select_check(_lib.load().mi_take(ctypes.byref(ad), ctypes.byref(idd), ctypes.byref(od), inner, ctypes.c_void_p(flag.ptr), None))
+    if flag.get()[0]:
+        raise IndexError("index out of range for an array of {} elements".format(a.size // inner))
+    return out
+
+
+def take(a, indices):
+    """a.ravel()[indices] for an int64 device index array (numpy.take without an axis; negative indices count from the end).
+    Whether every index is in range is checked on the device into a flag the host reads: an index out of range raises
+    IndexError, and no out-of-bounds read is ever issued."""
+    out = _take_rows(a, indices, 1)
+    return out.reshape(out.shape[:-1])
+
+
+def _argsort(a, descending, want_idx, want_sorted):
+    a = _select_input(a)
+    if a.ndim != 1:
+        raise ValueError("argsort and sort take 1-D arrays")
+    idx = ndarray(a.shape, np.int64) if want_idx else None
+    srt = ndarray(a.shape, a.dtype) if want_sorted else None
+    if a.size:
+        ad = a._desc()
+        idd = idx._desc() if want_idx else None
+        sd = srt._desc() if want_sorted else None
+        _select_check(_lib.load().mi_argsort(ctypes.byref(ad), ctypes.byref(idd) if want_idx else None,
+                                             ctypes.byref(sd) if want_sorted else None, int(bool(descending)), None))
+    return idx, srt
+
+
+def argsort(a, descending=False):
+    """Stable argsort of a 1-D array, int64: numpy.argsort(a, kind="stable") index for index; with `descending`
+    numpy.argsort(-a, kind="stable") (integers negate with wrap-around, as NumPy's do; bool negates logically).  -0.0 sorts
+    equal to +0.0; every NaN sorts last, the NaNs in their original order.  The input is not written."""
+    return _argsort(a, descending, True, False)[0]
+
+
+def sort(a):
+    """Sorted copy of a 1-D array: a[argsort(a)] (numpy.sort(a, kind="stable"))."""
+    return _argsort(a, False, False, True)[1]
+
+
 class Stream:
     """A hipStream besides the library's default stream (used for the halo
     exchange so that it overlaps the interior filtering)."""

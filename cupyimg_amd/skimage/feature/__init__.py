@@ -1,8 +1,11 @@
 """skimage.feature subset: the Hessian matrix and its eigenvalues (cupyimg/skimage/feature/corner.py:141-211, 260-458) on
 HIP kernels (csrc/ridges.hip), the Canny edge detector (cupyimg/skimage/feature/_canny.py) with its Sobel, magnitude and
-non-maximum-suppression stage as one kernel (csrc/edges.hip), and the structure tensor with the corner detectors built on it
-(corner.py:18-138, 384-425, 533-830; csrc/corners.hip)."""
+non-maximum-suppression stage as one kernel (csrc/edges.hip), the structure tensor with the corner detectors built on it
+(corner.py:18-138, 384-425, 533-830; csrc/corners.hip), and peak_local_max / corner_peaks (peak.py, corner.py:833-953) on the
+device compaction, sort and greedy-spacing kernels of csrc/select.hip."""
 import ctypes
+import functools
+import inspect
 import warnings
 
 import numpy as np
@@ -13,7 +16,8 @@ from ...scipy.ndimage import _support as S
 from ..filters import _img_as_float
 
 __all__ = ["hessian_matrix", "hessian_matrix_eigvals", "structure_tensor_eigenvalues", "canny", "structure_tensor",
-           "structure_tensor_eigvals", "corner_harris", "corner_shi_tomasi", "corner_foerstner", "corner_kitchen_rosenfeld"]
+           "structure_tensor_eigvals", "corner_harris", "corner_shi_tomasi", "corner_foerstner", "corner_kitchen_rosenfeld",
+           "peak_local_max", "corner_peaks"]
 
 
 def _as_float_device(image):
@@ -384,3 +388,276 @@ def canny(image, sigma=1.0, low_threshold=None, high_threshold=None, mask=None, 
     else:
         _, _, high_mask, low_mask = _canny_stage(smoothed, eroded, high_threshold, low_threshold)
     return ndi.binary_propagation(high_mask, structure=np.ones((3, 3), bool), mask=low_mask)
+
+
+# ------------------------------------------------------------------ peak_local_max, corner_peaks (peak.py, corner.py:833-953)
+_peak_launches = 0
+_P_NORMS = {np.inf: 0, 1: 1, 2: 2}
+_SPACING_FIRST_BATCH = 4          # rounds queued before the first look at the "still live" flag
+
+
+def last_peak_launches():
+    """Kernel launches of csrc/select.hip the last `peak_local_max`, `corner_peaks` or `_ensure_spacing` call of this process
+    queued (no-op spacing rounds included; the maximum filter and the reductions of the threshold are not counted): a
+    diagnostic for benchmarks and tests."""
+    return _peak_launches
+
+
+def _select_launches():
+    fn = S.lib().mi_debug_select_launches
+    fn.argtypes = []
+    fn.restype = ctypes.c_int
+    return fn()
+
+
+def _counts_launches(func):
+    """the outermost decorated call records the launches it queued"""
+    @functools.wraps(func)
+    def counted(*args, **kwargs):
+        global _peak_launches
+        if counted.depth:
+            return func(*args, **kwargs)
+        counted.depth += 1
+        try:
+            before = _select_launches()
+            try:
+                return func(*args, **kwargs)
+            finally:
+                _peak_launches = _select_launches() - before
+        finally:
+            counted.depth -= 1
+    counted.depth = 0
+    return counted
+
+
+def _removed_arg(name, version):
+    """FutureWarning when the deprecated argument `name` is passed at all (remove_arg of _shared/utils.py)"""
+    def wrap(func):
+        position = list(inspect.signature(func).parameters).index(name)
+
+        @functools.wraps(func)
+        def checked(*args, **kwargs):
+            if len(args) > position or name in kwargs:
+                warnings.warn("{0} argument is deprecated and will be removed in version {1}. To avoid this warning, please do not use "
+                              "the {0} argument. Please see {2} documentation for more details.".format(name, version, func.__name__),
+                              FutureWarning, stacklevel=2)
+            return func(*args, **kwargs)
+        return checked
+    return wrap
+
+
+def _p_norm_code(p_norm):
+    try:
+        return _P_NORMS[float(p_norm)]
+    except (KeyError, TypeError, ValueError):
+        raise ValueError("p_norm must be 1, 2 or inf on the device (exact integer distances), got {!r}".format(p_norm))
+
+
+def _integral_distance(value, name):
+    if isinstance(value, (bool, np.bool_)) or not np.isscalar(value) or not np.isfinite(value) or int(value) != value:
+        raise ValueError("{} must be an integer on the device (exact integer distances), got {!r}".format(name, value))
+    return int(value)
+
+
+def _get_excluded_border_width(ndim, min_distance, exclude_border):
+    """border widths per axis, every error of peak.py:87-117"""
+    if isinstance(exclude_border, bool):
+        return (min_distance if exclude_border else 0,) * ndim
+    if isinstance(exclude_border, int):
+        if exclude_border < 0:
+            raise ValueError("`exclude_border` cannot be a negative value")
+        return (exclude_border,) * ndim
+    if isinstance(exclude_border, tuple):
+        if len(exclude_border) != ndim:
+            raise ValueError("`exclude_border` should have the same length as the dimensionality of the image.")
+        for exclude in exclude_border:
+            if not isinstance(exclude, int):
+                raise ValueError("`exclude_border`, when expressed as a tuple, must only contain ints.")
+            if exclude < 0:
+                raise ValueError("`exclude_border` can not be a negative value")
+        return exclude_border
+    raise TypeError("`exclude_border` must be bool, int, or tuple with the same length as the dimensionality of the image.")
+
+
+def _check_peak_image(image):
+    """(ndim, dtype) of an image the peak functions take, before anything touches the device"""
+    if not isinstance(image, (core.ndarray, np.ndarray)):
+        image = np.asarray(image)
+    dtype = np.dtype(image.dtype)
+    if dtype == np.bool_ or dtype.kind not in "iuf":
+        raise TypeError("peak_local_max takes images of a real dtype, not {}".format(dtype))
+    if image.ndim < 1 or image.ndim > _lib.MI_MAX_NDIM:
+        raise ValueError("arrays of rank 1 to {}".format(_lib.MI_MAX_NDIM))
+    return image.ndim, dtype
+
+
+def _get_threshold(image, threshold_abs, threshold_rel):
+    """peak.py:74-84 with the image's minimum and maximum from the device reductions"""
+    lo, hi = S.min_max(image) if (threshold_abs is None or threshold_rel is not None) else (0.0, 0.0)
+    threshold = threshold_abs if threshold_abs is not None else lo
+    if threshold_rel is not None:
+        threshold = max(threshold, threshold_rel * float(hi))
+    return float(threshold)
+
+
+def _peak_candidates(image, image_max, threshold, border):
+    """(coords (K, ndim) int64 in raster order, values (K,)): the fused predicate through the count / write compaction; the
+    mask never exists in memory.  A "trivial" image (every voxel equal to its filtered maximum) has no candidates."""
+    lib = S.lib()
+    nbytes = ctypes.c_int64()
+    core._select_check(lib.mi_select_work_bytes(image.size, ctypes.byref(nbytes)))
+    work = core.empty((nbytes.value,), np.uint8)
+    total, equal = ctypes.c_int64(), ctypes.c_int64()
+    bw = (ctypes.c_int64 * _lib.MI_MAX_NDIM)(*[int(b) for b in border])
+    idesc, wdesc = image._desc(), work._desc()
+    mdesc = image_max._desc() if image_max is not None else None
+    mref = ctypes.byref(mdesc) if image_max is not None else None
+    core._select_check(lib.mi_peak_count(ctypes.byref(idesc), mref, threshold, bw, ctypes.byref(wdesc), ctypes.byref(total),
+                                         ctypes.byref(equal), None))
+    k = total.value
+    if image_max is not None and equal.value == image.size:
+        k = 0
+    coords, values = core.empty((k, image.ndim), np.int64), core.empty((k,), image.dtype)
+    if k:
+        cdesc, vdesc = coords._desc(), values._desc()
+        core._select_check(lib.mi_peak_write(ctypes.byref(idesc), mref, threshold, bw, ctypes.byref(wdesc), ctypes.byref(cdesc),
+                                             ctypes.byref(vdesc), None))
+    return coords, values
+
+
+@_counts_launches
+def _ensure_spacing(coords, shape, spacing, p_norm=np.inf, inclusive=False):
+    """The points of `coords` -- a (K, ndim) int64 device array of distinct points inside `shape`, in rank order -- that the
+    greedy walk of ensure_spacing (_shared/coord.py) keeps: every point not yet rejected rejects the later points at a
+    distance below `spacing` (`inclusive`: at or below it, the rule of corner_peaks, corner.py:929-945).  That is the
+    lexicographically first maximal independent set of the conflict graph, computed in rounds on the device (keep the live
+    points without a live conflicting point of lower rank, reject the live points in conflict with a kept one) with one
+    4-byte read per batch of rounds, and compacted in order.  Distances are exact integers (max |d|, sum |d|, sum d^2 against
+    spacing^2); p_norm other than 1, 2, inf and a non-integral spacing raise ValueError."""
+    p = _p_norm_code(p_norm)
+    spacing = _integral_distance(spacing, "spacing")
+    shape = tuple(int(s) for s in shape)
+    coords = core.ascontiguousarray(coords)
+    if coords.dtype != np.int64 or coords.ndim != 2 or coords.shape[1] != len(shape):
+        raise ValueError("coords must be a (K, {}) int64 array".format(len(shape)))
+    k = coords.shape[0]
+    if k == 0 or spacing < (0 if inclusive else 1) or (spacing == 0 and inclusive):
+        return coords
+    lib = S.lib()
+    grid = core.empty(shape, np.int32)
+    status = core.empty((k,), np.uint8)
+    cdesc, gdesc, sdesc = coords._desc(), grid._desc(), status._desc()
+    flag = ctypes.c_int()
+    core._select_check(lib.mi_spacing_init(ctypes.byref(cdesc), ctypes.byref(gdesc), ctypes.byref(sdesc), ctypes.byref(flag), None))
+    if flag.value:
+        raise ValueError("coords holds points outside shape {}".format(shape))
+    done, batch = 0, _SPACING_FIRST_BATCH
+    while True:
+        core._select_check(lib.mi_spacing_rounds(ctypes.byref(cdesc), ctypes.byref(gdesc), ctypes.byref(sdesc), spacing, p, int(inclusive),
+                                                 batch, ctypes.byref(flag), None))
+        done += batch
+        if not flag.value:
+            break
+        if done >= k:           # every round with a live point keeps at least the live point of lowest rank
+            raise RuntimeError("greedy spacing did not finish in {} rounds for {} points".format(done, k))
+        batch = min(2 * batch, 64, k - done)
+    keep = core.flatnonzero(status)
+    return coords if keep.shape[0] == k else core._take_rows(coords, keep, coords.shape[1])
+
+
+def _coords_to_mask(coords, shape):
+    out = core.empty(shape, np.bool_)
+    cdesc, odesc = coords._desc(), out._desc()
+    core._select_check(S.lib().mi_scatter_true(ctypes.byref(cdesc), ctypes.byref(odesc), None))
+    return out
+
+
+def _limit(coords, num_peaks):
+    if num_peaks is None or num_peaks == np.inf or coords.shape[0] <= num_peaks:
+        return coords
+    return coords[:max(int(num_peaks), 0)]
+
+
+@_counts_launches
+def _peak_local_max(image, min_distance, threshold_abs, threshold_rel, exclude_border, num_peaks, footprint, labels, p_norm):
+    """(coords, shape); every check before the first device call"""
+    if labels is not None:
+        raise NotImplementedError("labels= needs a device find_objects, which this library does not have yet")
+    ndim, dtype = _check_peak_image(image)
+    if footprint is not None:
+        footprint = core.host_copy(footprint) if isinstance(footprint, core.ndarray) else np.asarray(footprint)
+    if (footprint is None or footprint.size == 1) and min_distance < 1:
+        warnings.warn("When min_distance < 1, peak_local_max acts as finding image > max(threshold_abs, threshold_rel * max(image)).",
+                      RuntimeWarning, stacklevel=4)
+    border = _get_excluded_border_width(ndim, min_distance, exclude_border)
+    _p_norm_code(p_norm)
+    min_distance = _integral_distance(min_distance, "min_distance")
+    border = tuple(max(int(b), 0) for b in border)
+    if not isinstance(image, core.ndarray):
+        image = core.asarray(np.asarray(image))
+    if image.dtype == np.float16:
+        image = image.astype(np.float32)
+    image = core.ascontiguousarray(image)
+    if image.size == 0:
+        return core.empty((0, ndim), np.int64), image.shape
+    threshold = _get_threshold(image, threshold_abs, threshold_rel)
+    image_max = None
+    if (footprint is None and min_distance >= 1 or footprint is not None and footprint.size != 1) and image.size != 1:
+        if footprint is None:
+            image_max = ndi.maximum_filter(image, size=2 * min_distance + 1, mode="constant")
+        else:
+            image_max = ndi.maximum_filter(image, footprint=footprint.astype(bool), mode="constant")
+        image_max = core.ascontiguousarray(image_max)
+    coords, values = _peak_candidates(image, image_max, threshold, border)
+    if coords.shape[0] > 1:
+        order = core.argsort(values, descending=True)         # highest first, ties in raster order
+        coords = core._take_rows(coords, order, ndim)
+    coords = _ensure_spacing(coords, image.shape, min_distance, p_norm)
+    return _limit(coords, num_peaks), image.shape
+
+
+@_removed_arg("indices", "0.20")
+def peak_local_max(image, min_distance=1, threshold_abs=None, threshold_rel=None, exclude_border=True, indices=True, num_peaks=np.inf,
+                   footprint=None, labels=None, num_peaks_per_label=np.inf, p_norm=np.inf):
+    """Peaks of an image as a (K, ndim) int64 device array of coordinates, highest first (peak.py:120-345): the voxels equal
+    to the maximum over their (2 * min_distance + 1)-wide neighbourhood (or `footprint`), above the threshold
+    (`threshold_abs`, default the image's minimum, raised to `threshold_rel * max(image)`), outside the excluded border
+    (`exclude_border`: True = min_distance, an int, or one int per axis), thinned so that no two are closer than
+    `min_distance` in the `p_norm` metric, and cut to `num_peaks`.  With `indices=False` (deprecated, FutureWarning) a bool
+    array of the image's shape.  No peaks: a (0, ndim) array.  The image is not written.
+
+    Order contract: the candidates are sorted by `-value` with a stable sort, so peaks of equal value come in raster order
+    (the reference leaves the order of ties to cupy.argsort); the greedy thinning walks them in that order.
+
+    Everything runs on the device: the maximum filter, one fused predicate through a count / scan / scatter compaction (the
+    mask never exists in memory; one read sizes the result and tells whether the image is trivial), a stable radix sort, the
+    greedy thinning in rounds (`_ensure_spacing`), `[:num_peaks]`.  Peak memory: the image, its filtered maximum, the int32
+    map of the image's shape and two (key, index) pair buffers of the candidates.
+
+    Deviations: `labels=` raises NotImplementedError (the reference loops over find_objects regions on the host and writes
+    into the caller's image); `_prominent_peaks` is not provided (it needs regionprops); `p_norm` must be 1, 2 or inf and
+    `min_distance` an integer (ValueError otherwise: distances are exact integers); float16 images are computed in float32;
+    a NaN never is a peak and is skipped by the threshold's minimum and maximum; a negative `min_distance` excludes no
+    border; an empty result is (0, ndim), not (0, 2)."""
+    coords, shape = _peak_local_max(image, min_distance, threshold_abs, threshold_rel, exclude_border, num_peaks, footprint, labels, p_norm)
+    return coords if indices else _coords_to_mask(coords, shape)
+
+
+@_counts_launches
+def corner_peaks(image, min_distance=1, threshold_abs=None, threshold_rel=None, exclude_border=True, indices=True, num_peaks=np.inf,
+                 footprint=None, labels=None, *, num_peaks_per_label=np.inf, p_norm=np.inf):
+    """Peaks of a corner response (corner.py:833-953): `peak_local_max` with num_peaks=inf and the Chebyshev metric, then a
+    second greedy pass in which every peak not yet rejected rejects the later peaks at a distance of `min_distance` or less
+    in the `p_norm` metric (so connected peaks of one value collapse to the first in raster order), then `[:num_peaks]`.
+    Returns a (K, ndim) int64 device array, or a bool array with `indices=False`.
+
+    Order contract: that of `peak_local_max` (highest first, peaks of equal value in raster order); both greedy passes walk
+    the peaks in that order.
+
+    Deviations: those of `peak_local_max` (`labels=` raises NotImplementedError, `p_norm` must be 1, 2 or inf and
+    `min_distance` an integer, an empty result is (0, ndim))."""
+    _p_norm_code(p_norm)
+    coords, shape = _peak_local_max(image, min_distance, threshold_abs, threshold_rel, exclude_border, np.inf, footprint, labels, np.inf)
+    coords = _ensure_spacing(coords, shape, min_distance, p_norm, inclusive=True)
+    coords = _limit(coords, None if num_peaks is None or np.isinf(num_peaks) else num_peaks)
+    return coords if indices else _coords_to_mask(coords, shape)

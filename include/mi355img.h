@@ -909,6 +909,54 @@ int mi_slab_pipe_step(mi_slab_pipe pipe, int submit, int compute);
 int mi_slab_pipe_run(mi_slab_pipe pipe, int nsteps, int use_graph);
 int mi_slab_pipe_info(mi_slab_pipe pipe, int *graph_state, int *graph_steps, int *planes_ok);
 
+/* ---- selection, gather and sorting (csrc/select.hip): results whose size depends on the data.
+ * Limits shared by the family: C-contiguous arrays of any real dtype except float16, at most 2^31 - 1 elements
+ * (MI_ERR_UNSUPPORTED above, before anything is queued); empty inputs return MI_OK without a launch.  No kernel waits on
+ * another workgroup and no output position depends on the order in which waves arrive: the results are reproducible bit for
+ * bit.
+ *
+ * Compaction is a count call and a write call around one allocation of the caller's.  `work` is a 1-D uint8 array of at
+ * least mi_select_work_bytes(a.size) bytes, uninitialised; the count call leaves the per-tile counts, their exclusive scan and
+ * the total there, reads the total back into *total (the one synchronisation) and the write call, given the same array and
+ * the same `work`, recomputes the predicate and scatters.  The predicate is "nonzero in the array's own dtype": NaN counts,
+ * -0.0 does not.  layout 0: out is (K,) int64, the flat indices in raster order; 1: (K, ndim), the unravelled indices as rows
+ * (argwhere); 2: (ndim, K), as columns (nonzero).  K = *total; a shorter `out` receives the first entries only. */
+int mi_select_work_bytes(int64_t n, int64_t *bytes);
+int mi_select_count(const mi_array *a, const mi_array *work, int64_t *total, mi_stream stream);
+int mi_select_write(const mi_array *a, const mi_array *work, const mi_array *out, int layout, mi_stream stream);
+/* out[k, :] = a[indices[k], :] with `a` seen as (a.size / inner, inner) and int64 indices (negative ones count from the end).
+ * An index out of range sets *flag_dev (device int32, zeroed by the caller) to 1, reads nothing and stores 0. */
+int mi_take(const mi_array *a, const mi_array *indices, const mi_array *out, int64_t inner, int32_t *flag_dev, mi_stream stream);
+/* Stable argsort of a 1-D array: idx_out (int64) = numpy.argsort(a, kind="stable"), index for index; with `descending`
+ * numpy.argsort(-a, kind="stable") (integers negate with wrap-around, as NumPy's do; bool negates logically).  -0.0 sorts
+ * equal to +0.0 and every NaN last, in the original order.  sorted_out (the array's dtype) = a[idx_out].  Either output may be
+ * NULL.  An LSD radix sort, 8 bits a pass (as many passes as the dtype has bytes), of (key, index) pairs between two pooled
+ * buffers; a pass is a per-workgroup digit histogram, a scan and a stable scatter.  Nothing synchronises. */
+int mi_argsort(const mi_array *a, const mi_array *idx_out, const mi_array *sorted_out, int descending, mi_stream stream);
+/* Peak candidates of skimage.feature.peak_local_max (peak.py:37-71) through the same count / write pair: voxel i is a
+ * candidate when image[i] == image_max[i] (skipped when image_max is NULL), image[i] > threshold -- compared in the image's
+ * dtype for float32 / float64, in double for integers, as NumPy 2 evaluates `image > float(threshold)` -- and its index along
+ * every axis d lies in [border[d], shape[d] - border[d]) (border NULL: none).  *n_equal = the number of voxels with
+ * image == image_max (0 without image_max).  The write call stores the unravelled indices as (K, ndim) int64 rows in raster
+ * order and the voxels' values as (K,) of the image's dtype.  No bool images. */
+int mi_peak_count(const mi_array *image, const mi_array *image_max, double threshold, const int64_t *border, const mi_array *work,
+                  int64_t *total, int64_t *n_equal, mi_stream stream);
+int mi_peak_write(const mi_array *image, const mi_array *image_max, double threshold, const int64_t *border, const mi_array *work,
+                  const mi_array *coords_out, const mi_array *values_out, mi_stream stream);
+/* Greedy spacing (ensure_spacing of _shared/coord.py, the loop of corner.py:929-945) of K distinct points given in rank order
+ * as (K, ndim) int64 rows.  mi_spacing_init zeroes `map` (int32, the image's shape), stores rank + 1 at every point and sets
+ * status (K uint8) to 2 = live; *bad = 1 when a point lies outside the map (it is left out).  mi_spacing_rounds runs `nrounds`
+ * rounds of two launches: a live point is kept (status 1) when no live point of lower rank conflicts with it, then live points
+ * in conflict with a kept one are rejected (status 0); *live = 1 when a point was still live after the last round.  Two points
+ * conflict when their distance is < spacing (inclusive 0) or <= spacing (inclusive 1), in exact integers: max |d| for p_norm
+ * 0, sum |d| for 1, sum d^2 against spacing^2 for 2.  Rounds without live points change nothing.  Both calls synchronise
+ * (one 4-byte read). */
+int mi_spacing_init(const mi_array *coords, const mi_array *map, const mi_array *status, int *bad, mi_stream stream);
+int mi_spacing_rounds(const mi_array *coords, const mi_array *map, const mi_array *status, int64_t spacing, int p_norm, int inclusive,
+                      int nrounds, int *live, mi_stream stream);
+/* out (bool, C-contiguous) = false everywhere, true at the (K, out.ndim) int64 points inside it */
+int mi_scatter_true(const mi_array *coords, const mi_array *out, mi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

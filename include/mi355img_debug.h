@@ -104,7 +104,9 @@ int mi_debug_set_morphsnakes(int small_boxes, int force_generic);   /* csrc/morp
 int mi_debug_set_tvl1(int small_tiles, int force_generic);   /* csrc/tvl1.hip: small_tiles = 1: tvl1_reg_fused_kernel works on tiles of 3 x 8 voxels in chunks of 3 planes instead of the planner's, so that small arrays have seams along every axis; force_generic = 1: every mi_tvl1_reg call takes the per-voxel kernels (four launches, u^1 and p^1 in the scratch block) */
 int mi_debug_set_edges(int small_tiles, int force_generic);   /* csrc/edges.hip: small_tiles = 1: edge_fused_kernel works on boxes of 2 x 3 x 5 voxels (3 x 5 pixels) instead of the planner's, so that small arrays have seams along every axis; force_generic = 1: every mi_edge_filter call takes one mi_correlate_nd per edge axis plus the per-voxel kernels */
 int mi_debug_set_corners(int small_tiles, int force_generic);   /* csrc/corners.hip: small_tiles = 1: st_fused_kernel works on boxes of 2 x 3 x 5 voxels (3 x 5 pixels) instead of the planner's, so that small arrays have seams along every axis; force_generic = 1: every mi_structure_products call takes one st_pass_kernel launch per pass plus st_product_kernel */
-int mi_debug_morphsnakes_launches(void);    /* csrc/morphsnakes.hip: kernel launches queued by the mi_snake_* entry points since the library was loaded (a count, not a status) */
+int mi_debug_set_select(int small_tiles);   /* csrc/select.hip: small_tiles = 1: a workgroup's tile of the compaction and sort kernels is 64 elements (one wave) and a scan block 64 entries instead of 2048 / >= 4096 / 1024, so that an array of a few thousand elements spans many tiles and more than one level of the scan (arrays above 2^20 elements keep the planner's tiles); not to be flipped between a count call and its write call */
+int mi_debug_select_launches(void);         /* csrc/select.hip: kernel launches queued by its entry points since the library was loaded (a count, not a status) */
+int mi_debug_morphsnakes_launches(void);   /* csrc/morphsnakes.hip: kernel launches queued by the mi_snake_* entry points since the library was loaded (a count, not a status) */
 
 #ifdef __cplusplus
 }
