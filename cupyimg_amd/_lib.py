@@ -175,6 +175,11 @@ SIGNATURES = {
     "mi_spacing_init": [_arr, _arr, _arr, _ip, _vp],
     "mi_spacing_rounds": [_arr, _arr, _arr, ctypes.c_int64, _i, _i, _i, _ip, _vp],
     "mi_scatter_true": [_arr, _arr, _vp],
+    "mi_rp_extent": [_arr, _arr, _vp],
+    "mi_rp_moments": [_arr, _arr, _arr, _arr, _arr, _arr, _vp],
+    "mi_rp_finish": [_arr, _i, _arr, _arr, _arr, _vp],
+    "mi_rp_keep": [_arr, _arr, _arr, ctypes.c_int64, _i, _arr, _vp],
+    "mi_rp_crop": [_arr, _arr, ctypes.c_int64, _i64p, _arr, _vp],
     "mi_map_coordinates": [_arr, _arr, _arr, _i, _i, _d, _vp],
     "mi_affine_transform": [_arr, _arr, _dp, _i, _i, _d, _vp],
     "mi_spline_pad": [_arr, _arr, _i, _i, _d, _vp],

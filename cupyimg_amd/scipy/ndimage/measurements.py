@@ -18,10 +18,14 @@ from . import _support as S
 
 __all__ = [
     "label", "sum", "sum_labels", "mean", "variance", "standard_deviation", "minimum", "maximum",
-    "minimum_position", "maximum_position", "extrema", "center_of_mass", "histogram",
+    "minimum_position", "maximum_position", "extrema", "center_of_mass", "histogram", "find_objects",
 ]
 
 _MAX_VOXELS = 2 ** 31
+_MAX_LABEL = 2 ** 31 - 1
+# the region tables (csrc/regionprops.hip) have one row per label up to max_label; a table larger than this is refused
+# (a label image whose largest label is far above its number of regions wants relabelling, not gigabytes of empty rows)
+_TABLE_BYTES_CAP = 2 ** 31
 
 
 def _generate_binary_structure(rank, connectivity):
@@ -429,3 +433,77 @@ def histogram(input, min, max, bins, labels=None, index=None):
     for k, r in enumerate(rows):
         res[k] = r
     return res
+
+
+# ------------------------------------------------------------------ region tables (csrc/regionprops.hip)
+def _dtype_of(a):
+    return a.dtype if isinstance(a, core.ndarray) else np.asarray(a).dtype
+
+
+def _check_table_rows(max_label, row_bytes, what):
+    if max_label > _MAX_LABEL:
+        raise ValueError("{}: max_label {} is above 2**31 - 1".format(what, max_label))
+    if max_label * row_bytes > _TABLE_BYTES_CAP:
+        raise ValueError("{}: a table of {} rows of {} bytes is above the cap of {} bytes (one row per label up to the "
+                         "largest one: relabel the image sequentially)".format(what, max_label, row_bytes, _TABLE_BYTES_CAP))
+
+
+def _max_label(labels, what):
+    """(smallest, largest) label of a non-empty device array as Python ints: the existing min / max reduction, one small
+    read-back.  uint64 labels of 2**63 and up have no int64 the kernels could compare: ValueError."""
+    lo, hi = S.min_max(labels)
+    if labels.dtype == np.uint64 and hi >= 2.0 ** 63:
+        raise ValueError("{}: uint64 labels of 2**63 or more are not supported".format(what))
+    return int(lo), int(hi)
+
+
+def _region_extents(labels, max_label):
+    """int64 device table (max_label, 1 + 3 ndim) of the C-contiguous int32 / int64 device `labels` (ndim >= 1): voxel count |
+    smallest index per axis | largest index + 1 per axis | sum of the indices per axis.  Nothing synchronises."""
+    ext = core.empty((max_label, 1 + 3 * labels.ndim), np.int64)
+    la, ea = labels._desc(), ext._desc()
+    S.check(S.lib().mi_rp_extent(ctypes.byref(la), ctypes.byref(ea), None), ValueError)
+    return ext
+
+
+def find_objects(input, max_label=0):
+    """Bounding boxes of the labelled regions (scipy.ndimage.find_objects): a list of `max_label` tuples of slices, None
+    for a label no voxel carries.  One sweep of rp_extent_kernel over the labels and one read-back of its table.
+
+    max_label < 1 means the array's maximum (one more small read-back).  Any integer or bool dtype; floats raise TypeError
+    and an empty input ValueError, as SciPy.  Deviations, both ValueError: uint64 labels of 2**63 or more, and a max_label
+    above 2**31 - 1 or one whose table (max_label x (1 + 3 ndim) x 8 bytes) is above 2 GiB."""
+    dt = _dtype_of(input)
+    if dt.kind not in "biu":
+        raise TypeError("find_objects: labels must be of integer or bool dtype, got {}".format(dt))
+    if (input.size if isinstance(input, core.ndarray) else np.size(input)) == 0:
+        raise ValueError("zero-size array to reduction operation maximum which has no identity")
+    max_label = int(max_label)
+    ndim = input.ndim if isinstance(input, core.ndarray) else np.ndim(input)
+    if max_label >= 1:
+        _check_table_rows(max_label, 8 * (1 + 3 * max(ndim, 1)), "find_objects")
+    input = S.as_device(input)
+    if max_label < 1:
+        max_label = _max_label(input, "find_objects")[1]
+        if max_label < 1:
+            return []
+        _check_table_rows(max_label, 8 * (1 + 3 * max(ndim, 1)), "find_objects")
+    elif input.dtype == np.uint64:
+        _max_label(input, "find_objects")
+    labels = _as_int_labels(input)
+    if ndim == 0:
+        v = int(labels.reshape(1).get()[0])
+        return [() if k + 1 == v else None for k in range(max_label)]
+    ext = _region_extents(labels, max_label).get()
+    return _slices_of(ext, ndim)
+
+
+def _slices_of(ext, ndim):
+    """SciPy's list of slice tuples from the host copy of an extent table"""
+    out = []
+    for row in ext:
+        if row[0] == 0:
+            out.append(None)
+        else:
+            out.append(tuple(slice(int(row[1 + d]), int(row[1 + ndim + d]), None) for d in range(ndim)))
+    return out

@@ -1,12 +1,14 @@
 """skimage.measure.label on device arrays (cupyimg/skimage/measure/_label.py): a thin wrapper over the greyscale mode
-of scipy.ndimage.label -- neighbours connect only when their values are equal, `background` voxels get label 0."""
+of scipy.ndimage.label -- neighbours connect only when their values are equal, `background` voxels get label 0.
+regionprops and regionprops_table (the tables of csrc/regionprops.hip) live in ._regionprops."""
 import numpy as np
 
 from ...scipy.ndimage import _support as S
 from ...scipy.ndimage import measurements as _m
 from ... import core
+from ._regionprops import COL_DTYPES, OBJECT_COLUMNS, PROPS, RegionProperties, regionprops, regionprops_table
 
-__all__ = ["label"]
+__all__ = ["label", "regionprops", "regionprops_table", "RegionProperties", "PROPS", "COL_DTYPES", "OBJECT_COLUMNS"]
 
 
 def _get_structure(ndim, connectivity):

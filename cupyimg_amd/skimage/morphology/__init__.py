@@ -14,10 +14,11 @@ from ... import core, _lib, _pad
 from ...scipy import ndimage as ndi
 
 from ...scipy.ndimage import _support as S
+from ._misc import remove_small_holes, remove_small_objects      # misc.py:51-245, on the tables of csrc/regionprops.hip
 
 __all__ = ["erosion", "dilation", "opening", "closing", "white_tophat", "black_tophat", "binary_erosion",
            "binary_dilation", "binary_opening", "binary_closing", "square", "rectangle", "diamond", "disk", "cube",
-           "octahedron", "ball", "octagon", "star", "reconstruction"]
+           "octahedron", "ball", "octagon", "star", "reconstruction", "remove_small_objects", "remove_small_holes"]
 
 
 def _default_selem(ndim):

@@ -957,6 +957,40 @@ int mi_spacing_rounds(const mi_array *coords, const mi_array *map, const mi_arra
 /* out (bool, C-contiguous) = false everywhere, true at the (K, out.ndim) int64 points inside it */
 int mi_scatter_true(const mi_array *coords, const mi_array *out, mi_stream stream);
 
+/* ---- region tables of a label image (csrc/regionprops.hip): find_objects, regionprops, remove_small_objects.
+ * Labels are C-contiguous int32 / int64; row r of every table belongs to label r + 1, the tables have max_label rows, and
+ * labels <= 0 or above max_label belong to no region.  Every table is written in full by the call that fills it (pool memory
+ * arrives dirty).  No kernel waits on another workgroup, and the number of launches does not depend on max_label.  Nothing
+ * synchronises.
+ *
+ * mi_rp_extent: ext (int64, (max_label, 1 + 3 ndim)) = voxel count | smallest index per axis | largest index + 1 per axis |
+ * sum of the indices per axis; a label no voxel carries has count 0 (its minima are then -1, its maxima 0).  Integer atomics: exact, reproducible.
+ * Any rank from 1 to MI_MAX_NDIM. */
+int mi_rp_extent(const mi_array *labels, const mi_array *ext, mi_stream stream);
+/* mi_rp_moments (ranks 2 and 3): raw and / or central (float64, (max_label, 4^ndim), either may be NULL) = the moments up to
+ * order 3 per axis, M[p][q][r] = sum w dz^p dy^q dx^r, in box coordinates (index - smallest index): raw about 0, central about
+ * the region's centroid raw[1, 0, ..] / raw[0, 0, ..]; w = 1, or the intensity converted to double.  centres (float64,
+ * (max_label, 2, ndim)) receives the box origin and that centroid.  Unweighted: one sweep serves both tables (the centroid
+ * follows from ext).  Weighted: a sweep for raw, and one more for central, which needs raw.  Double atomics: exact while every
+ * term and partial sum is an integer below 2^53, otherwise the last bits depend on the arrival order. */
+int mi_rp_moments(const mi_array *labels, const mi_array *intensity, const mi_array *ext, const mi_array *raw, const mi_array *central,
+                  const mi_array *centres, mi_stream stream);
+/* mi_rp_finish: out (float64, (max_label, stride)) = the derived columns of skimage's RegionProperties in the reference's
+ * operation order, for ndim 2 (stride 40) or 3 (stride 96): bbox_area, extent, equivalent_diameter, centroid[ndim],
+ * local_centroid[ndim], moments_normalized[4^ndim], moments_hu[7], inertia_tensor[ndim^2], inertia_tensor_eigvals[ndim],
+ * major_axis_length, minor_axis_length, eccentricity, orientation.  raw: the WEIGHTED raw table (the two centroids are then
+ * the weighted ones), NULL for the unweighted columns; central NULL: the row is the short one, the columns before
+ * moments_normalized only (stride 7 in 2-D, 9 in 3-D).  Rows of absent labels and the 2-D-only columns in 3-D are NaN. */
+int mi_rp_finish(const mi_array *ext, int ndim, const mi_array *raw, const mi_array *central, const mi_array *out, mi_stream stream);
+/* mi_rp_keep, mode 0: out = src where ext[label - 1, 0] >= min_size, else 0 (src and out of one element size; any dtype);
+ * mode 1: out = (src == 0) as 0 / 1 (labels and ext unused); mode 2: out = !(ext[label - 1, 0] >= min_size) as 0 / 1. */
+int mi_rp_keep(const mi_array *labels, const mi_array *src, const mi_array *ext, int64_t min_size, int mode, const mi_array *out,
+               mi_stream stream);
+/* mi_rp_crop (ranks 1 to 3): out, a C-contiguous box at `origin`, = (labels[box] == label) as bool, or with an intensity image
+ * intensity[box] where that holds and 0 elsewhere, in the intensity's dtype. */
+int mi_rp_crop(const mi_array *labels, const mi_array *intensity, int64_t label, const int64_t *origin, const mi_array *out,
+               mi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

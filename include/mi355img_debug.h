@@ -107,6 +107,8 @@ int mi_debug_set_corners(int small_tiles, int force_generic);   /* csrc/corners.
 int mi_debug_set_select(int small_tiles);   /* csrc/select.hip: small_tiles = 1: a workgroup's tile of the compaction and sort kernels is 64 elements (one wave) and a scan block 64 entries instead of 2048 / >= 4096 / 1024, so that an array of a few thousand elements spans many tiles and more than one level of the scan (arrays above 2^20 elements keep the planner's tiles); not to be flipped between a count call and its write call */
 int mi_debug_select_launches(void);         /* csrc/select.hip: kernel launches queued by its entry points since the library was loaded (a count, not a status) */
 int mi_debug_morphsnakes_launches(void);   /* csrc/morphsnakes.hip: kernel launches queued by the mi_snake_* entry points since the library was loaded (a count, not a status) */
+int mi_debug_set_regionprops(int force_global);   /* csrc/regionprops.hip: force_global = 1: the run heads of rp_extent_kernel and rp_moments_kernel issue their atomics straight to the tables in global memory whatever the number of regions (no per-workgroup copies in LDS) */
+int mi_debug_regionprops_launches(void);    /* csrc/regionprops.hip: kernel launches queued by the mi_rp_* entry points since the library was loaded (a count, not a status) */
 
 #ifdef __cplusplus
 }
