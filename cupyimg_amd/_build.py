@@ -87,6 +87,7 @@ SOURCES = [
     ("corners.hip", ["-ffp-contract=off"]),
     ("select.hip", []),
     ("regionprops.hip", ["-ffp-contract=off"]),
+    ("threshold.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function",
           "-I" + os.path.join(os.path.dirname(HERE), "include")]

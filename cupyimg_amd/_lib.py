@@ -180,6 +180,11 @@ SIGNATURES = {
     "mi_rp_finish": [_arr, _i, _arr, _arr, _arr, _vp],
     "mi_rp_keep": [_arr, _arr, _arr, ctypes.c_int64, _i, _arr, _vp],
     "mi_rp_crop": [_arr, _arr, ctypes.c_int64, _i64p, _arr, _vp],
+    "mi_window_mean_std": [_arr, _ip, _i, _d, _d, _arr, _arr, _vp],
+    "mi_li_sums": [_arr, _d, _d, ctypes.c_int64, _vp, _vp],
+    "mi_min_adjacent_diff": [_arr, _d, _dp, _vp],
+    "mi_multiotsu_search": [_dp, _dp, _i, _i, _i64p, _dp, _vp],
+    "mi_compare": [_i, _arr, _arr, _i, _d, _i, ctypes.c_uint64, _arr, _vp],
     "mi_map_coordinates": [_arr, _arr, _arr, _i, _i, _d, _vp],
     "mi_affine_transform": [_arr, _arr, _dp, _i, _i, _d, _vp],
     "mi_spline_pad": [_arr, _arr, _i, _i, _d, _vp],

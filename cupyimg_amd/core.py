@@ -361,6 +361,71 @@ class ndarray:
         _copy(src, dst)
 
 
+    # ------------------------------------------------------------- ordering (csrc/threshold.hip: mi_compare)
+    def __gt__(self, other):
+        return _compare(self, other, 0)
+
+    def __ge__(self, other):
+        return _compare(self, other, 1)
+
+    def __lt__(self, other):
+        return _compare(self, other, 2)
+
+    def __le__(self, other):
+        return _compare(self, other, 3)
+
+
+_CMP_INT, _CMP_F32, _CMP_F64 = 0, 1, 2
+
+
+def _compare(a, other, op):
+    """a > / >= / < / <= other as a C-contiguous bool device array from one launch, compared as NumPy 2 compares
+    `a.get()` with `other`: in the common dtype of the two (a Python int or float is a weak scalar: a uint8 image against a
+    Python float compares in float64, a float32 image against one in float32), integers of any two dtypes exactly, NaN
+    false.  `other`: a Python or NumPy scalar, or a device array of a's shape; anything else is left to Python (TypeError).
+    float16 operands are widened to float32 (exact; no kernel computes in float16) and strided ones compacted first."""
+    scalar = None
+    if isinstance(other, ndarray):
+        if other.shape != a.shape:
+            raise ValueError("operands could not be broadcast together with shapes {} {} (comparisons take a scalar or an "
+                             "array of the same shape)".format(a.shape, other.shape))
+        common = np.result_type(a.dtype, other.dtype)
+        kinds = a.dtype.kind + other.dtype.kind
+    else:
+        if isinstance(other, np.ndarray) and other.ndim == 0:
+            other = other[()]
+        if not isinstance(other, (bool, int, float, np.bool_, np.integer, np.floating)):
+            return NotImplemented
+        common = np.result_type(a.dtype, other)
+        kinds = a.dtype.kind + ("b" if isinstance(other, (bool, np.bool_)) else "i" if isinstance(other, (int, np.integer)) else "f")
+        scalar = other
+    hi, lo, value = 0, 0, 0.0
+    if all(k in "biu" for k in kinds):
+        ctype = _CMP_INT                        # exact across signedness, as NumPy's mixed integer loops are
+        if scalar is not None:
+            v = int(scalar)
+            if v < -2 ** 63:
+                hi, lo = 0, 0                   # below every int64
+            elif v > 2 ** 64 - 1:
+                hi, lo = 2, 0                   # above every uint64
+            else:
+                hi, lo = int(v >= 0), v & (2 ** 64 - 1)
+    else:
+        ctype = _CMP_F64 if common == np.float64 else _CMP_F32
+        if scalar is not None:
+            value = float(common.type(scalar))  # the scalar in the common dtype, as NumPy converts it
+    lhs = ascontiguousarray(a.astype(np.float32) if a.dtype == np.float16 else a)
+    rhs = None
+    if scalar is None:
+        rhs = ascontiguousarray(other.astype(np.float32) if other.dtype == np.float16 else other)
+    out = ndarray(a.shape, np.bool_)
+    da, do = lhs._desc(), out._desc()
+    db = rhs._desc() if rhs is not None else None
+    _lib.check(_lib.load().mi_compare(op, ctypes.byref(da), ctypes.byref(db) if db is not None else None, ctype, value, hi, lo,
+                                      ctypes.byref(do), None), ValueError)
+    return out
+
+
 def _is_wide_integer(value):
     """an integer value a double does not hold exactly"""
     if isinstance(value, np.ndarray):

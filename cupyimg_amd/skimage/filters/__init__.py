@@ -1,7 +1,8 @@
 """skimage.filters subset: gaussian (cupyimg/skimage/filters/_gaussian.py:13-145), the Hessian ridge filters meijering, sato,
 frangi and hessian (cupyimg/skimage/filters/ridges.py) on the fused kernels of csrc/ridges.hip, the edge operators of
 cupyimg/skimage/filters/edges.py (sobel, scharr and prewitt on the fused kernel of csrc/edges.hip) and
-apply_hysteresis_threshold (cupyimg/skimage/filters/thresholding.py:1182-1227)."""
+apply_hysteresis_threshold (cupyimg/skimage/filters/thresholding.py:1182-1227); the threshold_* functions of that file live in
+_thresholding.py (csrc/threshold.hip) and are re-exported here."""
 import ctypes
 import math
 import warnings
@@ -575,3 +576,11 @@ def apply_hysteresis_threshold(image, low, high):
                                        ctypes.byref(had) if had is not None else None, low_s, high_s, ctypes.byref(ld),
                                        ctypes.byref(hd), None), ValueError)
     return ndi.binary_propagation(mask_high, structure=ndi.generate_binary_structure(image.ndim, 1), mask=mask_low)
+
+
+from ._thresholding import (_mean_std, threshold_isodata, threshold_li, threshold_local, threshold_mean, threshold_minimum,  # noqa: E402,F401
+                            threshold_multiotsu, threshold_niblack, threshold_otsu, threshold_sauvola, threshold_triangle,
+                            threshold_yen, try_all_threshold)
+from . import _thresholding  # noqa: E402
+
+__all__ += _thresholding.__all__

@@ -991,6 +991,45 @@ int mi_rp_keep(const mi_array *labels, const mi_array *src, const mi_array *ext,
 int mi_rp_crop(const mi_array *labels, const mi_array *intensity, int64_t label, const int64_t *origin, const mi_array *out,
                mi_stream stream);
 
+/* ---- skimage.filters thresholding and the ordering operators of the array layer (csrc/threshold.hip, -ffp-contract=off)
+ *
+ * mi_window_mean_std (_mean_std, threshold_niblack, threshold_sauvola; cupyimg/skimage/filters/thresholding.py:1003-1179): the
+ *   sums S of x and Q of x^2 over the window of window[d] (odd, >= 1) samples per axis centred on every sample, the image
+ *   extended as numpy.pad(mode="reflect") extends it (period 2 (n - 1) per axis, an axis of one sample repeats it) by index
+ *   arithmetic, then with n = prod(window), each operation rounded on its own:
+ *     m = S / n;  g2 = Q / n;  s = sqrt(g2 - m m < 0 ? 0 : g2 - m m)
+ *     kind 0: out0 = m, out1 = s;  kind 1: out0 = m - k s;  kind 2: out0 = m (1 + k (s / r - 1))      (out1 NULL for 1 and 2)
+ *   image: any dtype but float16, C-contiguous, rank 1 to 8; outputs float64.  bool and the integers of 16 bits or fewer are
+ *   summed in integer registers (exact); every other dtype as doubles, a window's terms added along the last axis first, each
+ *   axis from its lowest index, every partial sum from 0 -- on every route, so the routes agree bit for bit.  Ranks 2 and 3:
+ *   one launch of win_fused_kernel (a tile and its halo in LDS, sums axis by axis; volumes streamed plane by plane through a
+ *   ring of per-plane sums); other ranks, a window of 2^31 / max|x| samples or more, or after mi_debug_set_threshold(.., 1):
+ *   win_generic_kernel, one thread per output.  Nothing synchronises.
+ * mi_li_sums (threshold_li, :751-759): over the finite samples x of a C-contiguous image, with y = x - shift (integers:
+ *   x - shift_int in int64; floats: rounded to the image's dtype), result[0 .. 5] = count and sum of the y > threshold (y as a
+ *   double), count and sum of the others, min x, max x.  Counts are int64; sums and extrema int64 for integer images (exact),
+ *   double for float32 / float64.  Two launches (per-workgroup parts in a tree of fixed shape, then one workgroup over the
+ *   parts in index order): the same bits on every run.  bool, uint64 and float16 are converted by the caller.  Synchronises.
+ * mi_min_adjacent_diff: the smallest positive x[i + 1] - x[i] of a sorted 1-D array as a double (+inf: none); floats: of
+ *   the samples shifted as above, non-finite ones skipped.  Synchronises.
+ * mi_multiotsu_search (threshold_multiotsu, :1230-1341): cum_p / cum_s: nbins + 1 host doubles, the running sums from 0 of
+ *   the normalised histogram p and of index * p.  Every strictly increasing tuple t_1 < .. < t_{classes-1} <= nbins - 2 is
+ *   evaluated: the sum over the classes, from the lowest, of S_k^2 / P_k (differences of the tables; 0 where P_k = 0), in
+ *   float64.  thresholds (host, classes - 1) = the tuple of the largest sum, the lexicographically smallest among equals,
+ *   whatever order the workgroups finish in; best (may be NULL) = that sum.  classes 2 to 5, at most 2^34 tuples.  Synchronises.
+ * mi_compare: out (bool) = a op b, op 0 >, 1 >=, 2 <, 3 <=; b an array of a's shape or NULL: then the scalar.  ctype is the
+ *   common type the caller worked out as NumPy does: 0 integers, compared exactly across signedness (the scalar is
+ *   scalar_hi 2^64 + scalar_lo - 2^64, scalar_hi 0 .. 2: two's complement with one more bit either way); 1 float32 (operands
+ *   float32 holds exactly); 2 float64.  NaN compares false.  One launch; nothing synchronises. */
+int mi_window_mean_std(const mi_array *image, const int *window, int kind, double k, double r, const mi_array *out0,
+                       const mi_array *out1, mi_stream stream);
+int mi_li_sums(const mi_array *image, double threshold, double shift, int64_t shift_int, void *result, mi_stream stream);
+int mi_min_adjacent_diff(const mi_array *sorted, double shift, double *result, mi_stream stream);
+int mi_multiotsu_search(const double *cum_p, const double *cum_s, int nbins, int classes, int64_t *thresholds, double *best,
+                        mi_stream stream);
+int mi_compare(int op, const mi_array *a, const mi_array *b, int ctype, double scalar, int scalar_hi, uint64_t scalar_lo,
+               const mi_array *out, mi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
