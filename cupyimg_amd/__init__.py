@@ -9,7 +9,7 @@ from . import core  # noqa: F401
 from .core import (  # noqa: F401
     Event, Stream, argsort, argwhere, array, arrays_differ, asarray, ascontiguousarray, asnumpy, count_nonzero, device_count,
     device_name, empty, empty_like, flatnonzero, free_all_blocks, full, get_device, is_available, ndarray, nonzero, ones,
-    pool_stats, set_device, shares_memory, sort, synchronize, take, zeros, zeros_like,
+    pool_stats, set_device, shares_memory, sort, synchronize, take, unique, zeros, zeros_like,
 )
 
 __version__ = "0.1.0"

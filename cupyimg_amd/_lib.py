@@ -185,6 +185,15 @@ SIGNATURES = {
     "mi_min_adjacent_diff": [_arr, _d, _dp, _vp],
     "mi_multiotsu_search": [_dp, _dp, _i, _i, _i64p, _dp, _vp],
     "mi_compare": [_i, _arr, _arr, _i, _d, _i, ctypes.c_uint64, _arr, _vp],
+    "mi_find_boundaries": [_arr, _i, _i, _i, ctypes.c_int64, _arr, _vp],
+    "mi_find_boundaries_subpixel": [_arr, _arr, _vp],
+    "mi_paint_boundaries": [_arr, _arr, _dp, _dp, _vp],
+    "mi_map_array_table": [_arr, _arr, _arr, _arr, ctypes.c_uint64, ctypes.c_int64, _i, _vp],
+    "mi_map_array_search": [_arr, _arr, _arr, _arr, _arr, _vp],
+    "mi_unique_heads": [_arr, _arr, _vp],
+    "mi_unique_counts": [_arr, ctypes.c_int64, _arr, _vp],
+    "mi_unique_inverse": [_arr, _arr, _arr, _vp],
+    "mi_join_key": [_arr, _arr, ctypes.c_int64, _arr, _vp],
     "mi_map_coordinates": [_arr, _arr, _arr, _i, _i, _d, _vp],
     "mi_affine_transform": [_arr, _arr, _dp, _i, _i, _d, _vp],
     "mi_spline_pad": [_arr, _arr, _i, _i, _d, _vp],

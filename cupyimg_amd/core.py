@@ -794,6 +794,50 @@ def sort(a):
     return _argsort(a, False, False, True)[1]
 
 
+def unique(a, return_index=False, return_inverse=False, return_counts=False):
+    """numpy.unique of an integer or bool array of any shape, flattened: the sorted distinct values, and on request the
+    index of each value's first occurrence, the inverse (of the input's shape, as NumPy 2 gives it) and the counts, all
+    intp.  A stable sort, head flags where a sorted key differs from its predecessor (csrc/segment.hip), then the count /
+    scan / scatter compaction of csrc/select.hip over the flags.  Float arrays raise TypeError: NumPy does not define
+    which of -0.0 / +0.0 represents the pair."""
+    if not isinstance(a, ndarray):
+        a = asarray(a) if hasattr(a, "__cuda_array_interface__") else np.asarray(a)
+    if a.dtype.kind not in "iub":
+        raise TypeError("unique takes integer and bool arrays, not {}".format(a.dtype))
+    a = asarray(a)
+    flat = _select_input(a).reshape(-1)
+    n = flat.size
+    lib = _lib.load()
+    if n == 0:
+        values = ndarray((0,), a.dtype)
+        index = counts = pos = perm = None
+    else:
+        perm, srt = _argsort(flat, False, True, True)
+        heads = ndarray((n,), np.bool_)
+        sd, hd = srt._desc(), heads._desc()
+        _select_check(lib.mi_unique_heads(ctypes.byref(sd), ctypes.byref(hd), None))
+        k, work = _select_count(heads)
+        pos = _select_write(heads, work, ndarray((k,), np.int64), 0)
+        values = take(srt, pos)
+    out = [values]
+    if return_index:
+        out.append(ndarray((0,), np.int64) if n == 0 else take(perm, pos))
+    if return_inverse:
+        inverse = ndarray(a.shape, np.int64)
+        if n:
+            flat_inv = inverse.reshape(-1)
+            pd, qd, fd = pos._desc(), perm._desc(), flat_inv._desc()
+            _select_check(lib.mi_unique_inverse(ctypes.byref(pd), ctypes.byref(qd), ctypes.byref(fd), None))
+        out.append(inverse)
+    if return_counts:
+        counts = ndarray(values.shape, np.int64)
+        if n:
+            pd, cd = pos._desc(), counts._desc()
+            _select_check(lib.mi_unique_counts(ctypes.byref(pd), n, ctypes.byref(cd), None))
+        out.append(counts)
+    return out[0] if len(out) == 1 else tuple(out)
+
+
 class Stream:
     """A hipStream besides the library's default stream (used for the halo
     exchange so that it overlaps the interior filtering)."""

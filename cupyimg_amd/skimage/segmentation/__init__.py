@@ -19,6 +19,8 @@ __all__ = [
     "disk_level_set",
     "checkerboard_level_set",
 ]
+# find_boundaries, mark_boundaries, relabel_sequential and join_segmentations are imported at the end of this file from
+# _boundaries.py and _join.py, whose `__all__` list them: tests/test_morphsnakes_host.py pins this list to the snakes.
 
 _STATE_BYTES = 64                                   # MI_SNAKE_STATE_BYTES
 _WORK_BYTES = _STATE_BYTES + 32 * 65536             # MI_SNAKE_WORK_BYTES
@@ -365,3 +367,6 @@ def morphological_geodesic_active_contour(gimage, iterations, init_level_set="ci
 
 # the default no-op callbacks, recognised by identity: nothing is copied for them
 _DEFAULT_CALLBACKS = (morphological_chan_vese.__defaults__[-1], morphological_geodesic_active_contour.__defaults__[-1])
+
+from ._boundaries import find_boundaries, last_boundary_launches, mark_boundaries  # noqa: E402,F401
+from ._join import join_segmentations, relabel_sequential  # noqa: E402,F401

@@ -1030,6 +1030,43 @@ int mi_multiotsu_search(const double *cum_p, const double *cum_s, int nbins, int
 int mi_compare(int op, const mi_array *a, const mi_array *b, int ctype, double scalar, int scalar_hi, uint64_t scalar_lo,
                const mi_array *out, mi_stream stream);
 
+/* ---- skimage.segmentation boundaries and relabelling, skimage.util.map_array, unique (csrc/segment.hip).  Integer compares
+ * and integer atomic minima only: every result is the same bits on every run.  Nothing synchronises.
+ *
+ * mi_find_boundaries (find_boundaries, cupyimg/skimage/segmentation/boundaries.py:160-180): labels of any integer dtype or bool
+ *   (bool as uint8), C-contiguous, rank 1 to 8; out bool.  N1(p): neighbours at city-block distance <= connectivity, N(p): the
+ *   3^ndim window, both clamped to the array; MAX the dtype's largest value; g(v) = MAX where v == background, else v.
+ *     mode 0 thick: some q in N1(p) has L[q] != L[p];  mode 1 inner: thick and L[p] != background;
+ *     mode 2 outer: thick and (L[p] == background or max over N of L != min over N of g(L))
+ *   has_background 0: the background is no value of the dtype (no voxel is background); else `background` holds its bits.
+ *   Ranks 2 and 3: one launch on a core box plus halo in LDS; other ranks or mi_debug_set_boundaries(.., 1): one thread a voxel.
+ * mi_find_boundaries_subpixel (:9-47): out has 2 s - 1 samples per axis.  An element with every coordinate even is false; any
+ *   other is true when {MAX} + {0 if a coordinate is 0 or 2 s - 2} + {labels of the pixels its 3^ndim window covers: c / 2 along
+ *   an even coordinate c, (c - 1) / 2 and (c + 1) / 2 along an odd one} has more than two distinct values.
+ * mi_paint_boundaries (mark_boundaries, :249-252): image (M, N, 3) float32 / float64, boundaries (M, N) bool: the colour where
+ *   the boundary is set; with outline_color, that colour where it is not but one of its 3 x 3 neighbours (clamped) is.
+ * mi_map_array_table / mi_map_array_search (cupyimg/skimage/util/_map_array.py): out[i] = output_vals[j] for the lowest j with
+ *   keys[j] == input[i], zero bits without one.  input and keys: one integer dtype; output_vals and out: one dtype of 1 to 8
+ *   bytes.  Table: key_min is the smallest key as an order-preserving unsigned value (signed dtypes: the sign-extended value with
+ *   bit 63 flipped), range = largest - smallest + 1; a table of range int32 from the pool is filled, set by atomicMin and gathered
+ *   through (use_lds: each workgroup copies it to LDS first; range <= 16384).  Search: sorted_keys ascending, perm[k] the
+ *   position of sorted_keys[k] in the caller's keys (a stable sort), output_vals in the caller's order.
+ * mi_unique_heads: heads[i] = i == 0 or sorted[i] != sorted[i - 1] (bits).  mi_unique_counts: counts[k] = pos[k + 1] - pos[k],
+ *   the last against n.  mi_unique_inverse: inverse[perm[i]] = (number of k with pos[k] <= i) - 1.
+ * mi_join_key: key (int64) = mul * r1 + r2 for integer fields of one shape. */
+int mi_find_boundaries(const mi_array *labels, int connectivity, int mode, int has_background, int64_t background, const mi_array *out,
+                       mi_stream stream);
+int mi_find_boundaries_subpixel(const mi_array *labels, const mi_array *out, mi_stream stream);
+int mi_paint_boundaries(const mi_array *boundaries, const mi_array *image, const double *color, const double *outline_color, mi_stream stream);
+int mi_map_array_table(const mi_array *input, const mi_array *keys, const mi_array *output_vals, const mi_array *out, uint64_t key_min,
+                       int64_t range, int use_lds, mi_stream stream);
+int mi_map_array_search(const mi_array *input, const mi_array *sorted_keys, const mi_array *perm, const mi_array *output_vals,
+                        const mi_array *out, mi_stream stream);
+int mi_unique_heads(const mi_array *sorted, const mi_array *heads, mi_stream stream);
+int mi_unique_counts(const mi_array *pos, int64_t n, const mi_array *counts, mi_stream stream);
+int mi_unique_inverse(const mi_array *pos, const mi_array *perm, const mi_array *inverse, mi_stream stream);
+int mi_join_key(const mi_array *r1, const mi_array *r2, int64_t mul, const mi_array *key, mi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
