@@ -244,6 +244,8 @@ extern "C" int mi_debug_set_rank_median(int enabled) { g_rank_median = enabled; 
 extern "C" int mi_debug_set_rank_sorted(int enabled) { g_rank_sorted = enabled; return MI_OK; }
 static mi::Knob g_minmax_tiled{1};
 extern "C" int mi_debug_set_minmax_tiled(int enabled) { g_minmax_tiled = enabled; return MI_OK; }
+static mi::Knob g_minmax_fast3{1};    // test hook: 0 = mi_minmax_nd never takes the rank <= 3 geometry (minmax3_kernel)
+extern "C" int mi_debug_set_minmax_fast3(int enabled) { g_minmax_fast3 = enabled; return MI_OK; }
 
 extern "C" {
 
@@ -271,6 +273,7 @@ int mi_minmax1d(const mi_array *in, const mi_array *out, int axis, int size, int
     const int geom = line_grid(total, n, inner, &grid, &block);
     if (geom == 0) grid_for(total, 256, &grid);
     const bool big = total >= ((int64_t)1 << 31) - 256 * 8192;
+    note_kernel("mi::minmax1d_kernel<%s> size=%d geom=%d", big ? "int64" : "int32", size, geom);
     return dispatch_dtype(in->dtype, [&]<typename T>() -> int {
         const T *ip = (const T *)in->data;
         if (big)
@@ -314,7 +317,7 @@ int mi_minmax_nd(const mi_array *in, const mi_array *out, const uint8_t *footpri
 
     Taps3Builder t3;
     Taps3 tt3;
-    const bool fast3 = Taps3Builder::eligible(in, fshape);
+    const bool fast3 = g_minmax_fast3 && Taps3Builder::eligible(in, fshape);
     TapBuilder tb;
     TapTable tt;
     if (fast3) {
@@ -344,11 +347,14 @@ int mi_minmax_nd(const mi_array *in, const mi_array *out, const uint8_t *footpri
         else cv = (double)(T)(int64_t)cval;
         const T *ip = (const T *)in->data;
         if (fast3) {
+            note_kernel("mi::minmax3_kernel ntaps=%d structure=%d (rank <= 3 geometry, %s tap table)", tt3.ntaps, structure != nullptr,
+                        tt3.inl ? "inline" : "device-buffer");
             hipLaunchKernelGGL((minmax3_kernel<T>), grid3(t3.g), dim3(64, 4, 1), taps3_lds_bytes(tt3), s, ip, out->data, out->dtype, t3.g,
                                tt3, mode, cv, is_max);
             MI_HIP(hipGetLastError());
             return MI_OK;
         }
+        note_kernel("mi::minmax_nd_kernel<%d> ntaps=%d structure=%d", tb.g.ndim == 3 ? 3 : MI_MAX_NDIM, tt.ntaps, structure != nullptr);
         if (tb.g.ndim == 3)
             hipLaunchKernelGGL((minmax_nd_kernel<T, 3>), grid, dim3(256), 0, s, ip, out->data, out->dtype, tb.g,
                                tt, total, mode, cv, is_max);

@@ -66,6 +66,7 @@ int mi_debug_set_bitmorph_table(int on);              /* 1: the run-time structu
 int mi_debug_set_bitmorph(int on, int ty, int nzc);   /* csrc/bitmorph3d.hip: 0 = byte kernels; ty / nzc > 0 override the tile planner */
 int mi_debug_set_stencil(int on);             /* csrc/correlate_nd.hip: 0 = generic n-D correlate */
 int mi_debug_set_minmax_tiled(int on);
+int mi_debug_set_minmax_fast3(int on);        /* csrc/minmax.hip: 0 = mi_minmax_nd never takes the rank <= 3 geometry (minmax3_kernel) */
 int mi_debug_set_rank_sorted(int on);
 int mi_debug_set_rank_median(int on);
 int mi_debug_set_u8_fused(int k);

@@ -334,6 +334,29 @@ _filter("minmax/untiled-footprint", "grey_dilation", _f32((12, 20, 70), 50), exa
 _STRUCT = np.random.default_rng(52).standard_normal((3, 3, 3))
 _filter("minmax/nd-structure", "grey_dilation", _f64((9, 10, 33), 53), exact, ref_mod=_sndi, structure=_STRUCT)
 _filter("minmax/nd-structure-erosion-2d", "grey_erosion", _f64((21, 67), 54), exact, ref_mod=_sndi, structure=_STRUCT[0], mode="wrap")
+
+
+def _grey_fuzz_cases(count=100):
+    """the first `count` cases of the grey-morphology draw (tests/helpers/grey_ref.py) that take a window with holes or a
+    structure, against the draw's own reference: the generic kernels of csrc/minmax.hip at every rank, dtype and output form.
+    Every other case of rank <= 3 runs outside the rank <= 3 geometry (minmax_nd_kernel<3>)."""
+    from helpers import grey_ref as gr
+    picked = [(i, c) for i, c in enumerate(gr.drawn()) if c["wkind"] in ("holes", "structure", "footprint+structure") and not c["illegal"]]
+    for k, (i, case) in enumerate(picked[:count]):
+        generic3 = len(case["shape"]) <= 3 and k % 2 == 1
+        route = None
+        if gr.has_structure(case):
+            route = "minmax_nd_kernel<8>" if len(case["shape"]) > 3 else "minmax_nd_kernel<3>" if generic3 else "minmax3_kernel"
+
+        def call(gpu, x, case=case):
+            ret, out, _ = gr.call(_ndi(), case, to_array=gpu.asarray, x=x)
+            assert out is None or ret is out
+            return ret
+        _add("minmax/grey-fuzz-{:03d}-{}-rank{}-{}{}".format(i, case["func"], len(case["shape"]), case["dtype"], "-generic3" if generic3 else ""),
+             lambda case=case: (case["x"].copy(),), call, lambda x, case=case: gr.reference(case), exact, knobs=[("mi_debug_set_minmax_fast3", (0,), (1,))] if generic3 else (), route=route)
+
+
+_grey_fuzz_cases()
 for _fn in ("morphological_gradient", "morphological_laplace", "white_tophat", "black_tophat"):
     _filter("minmax/" + _fn + "-uint8", _fn, _ints((12, 20, 70), 55, np.uint8), exact, ref_mod=_sndi, size=3)
     _filter("minmax/" + _fn + "-float32", _fn, _f32((9, 10, 33), 56), exact, ref_mod=_sndi, size=(3, 5, 3))
