@@ -165,6 +165,7 @@ SIGNATURES = {
     "mi_threshold_masks":[_arr, _arr, _arr, _d, _d, _arr, _arr, _vp],
     "mi_structure_products": [_arr, _arr, _i, _i, _i, _d, _vp],
     "mi_corner_response": [_arr, _arr, _arr, _i, _d, _d, _vp],
+    "mi_match_template": [_arr, _arr, _arr, _i, _i, _d, _d, _d, _vp],
     "mi_select_work_bytes": [ctypes.c_int64, _i64p],
     "mi_select_count": [_arr, _arr, _i64p, _vp],
     "mi_select_write": [_arr, _arr, _arr, _i, _vp],

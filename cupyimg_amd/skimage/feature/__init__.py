@@ -2,7 +2,8 @@
 HIP kernels (csrc/ridges.hip), the Canny edge detector (cupyimg/skimage/feature/_canny.py) with its Sobel, magnitude and
 non-maximum-suppression stage as one kernel (csrc/edges.hip), the structure tensor with the corner detectors built on it
 (corner.py:18-138, 384-425, 533-830; csrc/corners.hip), and peak_local_max / corner_peaks (peak.py, corner.py:833-953) on the
-device compaction, sort and greedy-spacing kernels of csrc/select.hip."""
+device compaction, sort and greedy-spacing kernels of csrc/select.hip, and match_template (template.py; _template.py here, one
+launch of csrc/template.hip)."""
 import ctypes
 import functools
 import inspect
@@ -14,10 +15,11 @@ from ... import core, _lib
 from ...scipy import ndimage as ndi
 from ...scipy.ndimage import _support as S
 from ..filters import _img_as_float
+from ._template import match_template
 
 __all__ = ["hessian_matrix", "hessian_matrix_eigvals", "structure_tensor_eigenvalues", "canny", "structure_tensor",
            "structure_tensor_eigvals", "corner_harris", "corner_shi_tomasi", "corner_foerstner", "corner_kitchen_rosenfeld",
-           "peak_local_max", "corner_peaks"]
+           "peak_local_max", "corner_peaks", "match_template"]
 
 
 def _as_float_device(image):

@@ -782,6 +782,27 @@ int mi_threshold_masks(const mi_array *image, const mi_array *low, const mi_arra
 int mi_structure_products(const mi_array *image, const mi_array *out, int products, int reverse, int mode, double cval, mi_stream stream);
 int mi_corner_response(const mi_array *elems, const mi_array *out0, const mi_array *out1, int kind, double k, double eps, mi_stream stream);
 
+/* skimage.feature.match_template (cupyimg/skimage/feature/template.py:125-205; csrc/template.hip): the normalised cross-correlation
+ * of an image (rank 2) or a volume (rank 3) with a template of the same rank, one launch.
+ *   image: C-contiguous uint8, uint16, int16, float32 or float64 (other dtypes: MI_ERR_UNSUPPORTED with nothing queued; the caller
+ *   converts); tmpl: C-contiguous float64, 1 <= tmpl.shape[a] <= image.shape[a]; out: C-contiguous float64 of image.shape
+ *   (pad_input != 0) or image.shape - tmpl.shape + 1.
+ *   mode: the index map that numpy.pad's mode of the reference amounts to -- 'constant' MI_MODE_CONSTANT (cval), 'edge'
+ *   MI_MODE_NEAREST, 'reflect' MI_MODE_MIRROR, 'symmetric' MI_MODE_REFLECT, 'wrap' MI_MODE_GRID_WRAP (MI_MODE_WRAP means the same) --
+ *   applied as often as it takes: the template may be as long as the axis.
+ *   Per axis the window of output index o starts at image index o - t / 2 (pad_input) or o, t = tmpl.shape[a].  Over the window,
+ *   every sample converted to double first, every product and sum a double rounded on its own, the taps in raster order:
+ *     x = x + I * T;   s1 = s1 + I;   s2 = s2 + I * I
+ *     num = x - s1 * mean;   d = s2 - (s1 * s1) / V;   d = d * ssd;   d = d < 0 ? 0 : d (a NaN stays);   den = sqrt(d)
+ *     out = den > DBL_EPSILON ? num / den : 0.0
+ *   mean, ssd: the template's mean and sum of squared deviations from it, formed by the caller; V = tmpl.size.  A window that holds
+ *   a NaN or an infinity gives 0.0.
+ *   mt_fused_kernel stages a tile's windows in LDS and walks templates whose box does not fit in slabs; mt_generic_kernel (one thread
+ *   per output, the same bits) runs after mi_debug_set_match_template(1) and for templates more than about 690 columns wide.
+ * Nothing synchronises and nothing is read by the host. */
+int mi_match_template(const mi_array *image, const mi_array *tmpl, const mi_array *out, int pad_input, int mode, double cval, double mean,
+                      double ssd, mi_stream stream);
+
 /* ------------------------------------------------------------------ */
 /* K5: interpolation, spline order 0 and 1                              */
 /* ------------------------------------------------------------------ */
