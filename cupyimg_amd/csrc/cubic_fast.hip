@@ -715,7 +715,6 @@ struct MapBoxParams {
     int nz, ny, nx, oz, oy, ox;
     int mode, npad;
     float cval;
-    int dbg;
 };
 
 constexpr int kMapBoxBytes = 64 * 1024;
@@ -780,7 +779,7 @@ cubic3_mapbox_kernel(const float *__restrict__ in, const C *__restrict__ coords,
     const int bz = red[3] - b0z + 1, by = red[4] - b0y + 1, bx = (red[5] - b0x + 1 + 3) & ~3;
     const bool any_plain = red[3] >= red[0];
     const long long floats = any_plain ? (long long)bz * by * bx : 0;
-    const bool fits = any_plain && floats * 4 <= (long long)kMapBoxBytes && !(q.dbg & 2);
+    const bool fits = any_plain && floats * 4 <= (long long)kMapBoxBytes;
     // ---- stage the box
     if (fits) {
         const unsigned cpr = (unsigned)bx >> 2;
@@ -906,7 +905,7 @@ cubic3_mapbox_kernel(const float *__restrict__ in, const C *__restrict__ coords,
 
 // false = not taken (small outputs, rows that are not whole 16-byte vectors, volumes beyond 32-bit offsets)
 bool launch_cubic_mapbox(const float *in, const void *coords, int coords_f64, float *out, const int shape[3], const int oshape[3], int mode, double cval, int npad,
-                         hipStream_t s, int *rc, int dbg)
+                         hipStream_t s, int *rc)
 {
     *rc = MI_OK;
     MapBoxParams q;
@@ -914,7 +913,7 @@ bool launch_cubic_mapbox(const float *in, const void *coords, int coords_f64, fl
     q.oz = oshape[0]; q.oy = oshape[1]; q.ox = oshape[2];
     if ((long long)q.oz * q.oy * q.ox < (1 << 18) || (q.ox & 3) || ((uintptr_t)out & 15) || ((uintptr_t)in & 15) || (q.nx & 3)) return false;
     if ((long long)q.nz * q.ny * q.nx * 4 >= (1LL << 31)) return false;
-    q.mode = mode; q.npad = npad; q.cval = (float)cval; q.dbg = dbg & 14;
+    q.mode = mode; q.npad = npad; q.cval = (float)cval;
     const dim3 grid((unsigned)((q.ox + kBoxT - 1) / kBoxT), (unsigned)((q.oy + kBoxT - 1) / kBoxT), (unsigned)((q.oz + kBoxT - 1) / kBoxT));
     if (grid.y > 65535 || grid.z > 65535) return false;
     const size_t lds = kMapBoxBytes + 64 + 8 * 256 * sizeof(float);
@@ -1194,7 +1193,6 @@ struct CubBoxParams {
     double cmin[3];
     int mode, npad;
     float cval;
-    int dbg;                     // timing ablations (0 in production): 2 = no second phase, 4 = no taps, 8 = no box DMA
 };
 
 __global__ void __launch_bounds__(512, 4)          // four waves per SIMD = two workgroups per CU (one computes while the other's box is in flight)
@@ -1238,7 +1236,7 @@ cubic3_box_kernel(const float *__restrict__ in, float *__restrict__ out, const C
             bool ok = ch < (unsigned)q.nchunks;
             if (!inside) ok = ok && b0[0] + (int)rz < q.nz && b0[1] + (int)ry < q.ny && b0[2] + 4 * (int)c4 < q.nx;
             const unsigned voff = ok ? rz * plane_b + ry * row_b + c4 * 16u : 0x80000000u;
-            if (!(q.dbg & 8)) cz_dma16(rin, voff, base, (unsigned)((wave << 6) + (j << 9)) * 16u, ~0ull);
+            cz_dma16(rin, voff, base, (unsigned)((wave << 6) + (j << 9)) * 16u, ~0ull);
         }
     }
     for (int e = tid; e < T * T * 3; e += 512) {
@@ -1279,8 +1277,6 @@ cubic3_box_kernel(const float *__restrict__ in, float *__restrict__ out, const C
             float val;
             if (out_c) {
                 val = q.cval;
-            } else if (held && (q.dbg & 4)) {
-                val = (float)(p0 + p1 + p2);
             } else if (held) {
                 float wz_[4], wy_[4], wx_[4];
                 cubic3_weights((float)(p0 - f0), wz_);
@@ -1345,7 +1341,7 @@ cubic3_box_kernel(const float *__restrict__ in, float *__restrict__ out, const C
     int *qcount = reinterpret_cast<int *>(tiles);
     if (tid == 0) *qcount = 0;
     __syncthreads();
-    if (todo != 0u && !(q.dbg & 2)) {
+    if (todo != 0u) {
 #pragma unroll 1
         for (int kl = 0; kl < 8; kl++) {
             if (!((todo >> kl) & 1u)) continue;
@@ -1376,7 +1372,7 @@ cubic3_box_kernel(const float *__restrict__ in, float *__restrict__ out, const C
 
 // plan + launch; false = not taken (diagonal / decoupled matrices have better kernels; box too large; small outputs)
 bool launch_cubic_box(const float *in, float *out, const int shape[3], const int oshape[3], const double *mat, int mode, double cval, int npad,
-                      hipStream_t s, int *rc, int dbg)
+                      hipStream_t s, int *rc)
 {
     *rc = MI_OK;
     CubBoxParams q;
@@ -1398,8 +1394,7 @@ bool launch_cubic_box(const float *in, float *out, const int shape[3], const int
     for (int a = 0; a < 2; a++) if (dim[a] > n[a]) dim[a] = n[a];
     if (dim[2] > ((n[2] + 3) & ~3) + 4) dim[2] = ((n[2] + 3) & ~3) + 4;
     const long long floats = (long long)dim[0] * dim[1] * dim[2];
-    const long long budget = (dbg >> 4) > 0 ? (long long)(dbg >> 4) * 1024 : (long long)kBoxBytesMax;       // test hook: knob >> 4 = budget in KiB
-    if (floats * 4 > budget || (floats / 4 + 511) / 512 > kBoxRoundsMax) return false;
+    if (floats * 4 > (long long)kBoxBytesMax || (floats / 4 + 511) / 512 > kBoxRoundsMax) return false;
     q.bz = dim[0]; q.by = dim[1]; q.bx = dim[2];
     q.nchunks = (int)(floats / 4);
     {
@@ -1414,7 +1409,6 @@ bool launch_cubic_box(const float *in, float *out, const int shape[3], const int
         q.cmin[a] = c;
     }
     q.mode = mode; q.npad = npad; q.cval = (float)cval;
-    q.dbg = dbg & 14;
     const dim3 grid((unsigned)((q.ox + kBoxT - 1) / kBoxT), (unsigned)((q.oy + kBoxT - 1) / kBoxT), (unsigned)((q.oz + kBoxT - 1) / kBoxT));
     if (grid.y > 65535 || grid.z > 65535) return false;
     const size_t lds = (((size_t)q.nchunks * 16 + 8191) & ~(size_t)8191) + kBoxT * kBoxT * 3 * sizeof(double) + 8 * 256 * sizeof(float);

@@ -982,11 +982,11 @@ cubic3_zstream_kernel(const float *__restrict__ in, float *__restrict__ out, con
 }
 
 Knob g_cubic_box{1};          // 0 = the gather kernel for matrices that couple all three axes; 1 = cubic3_box_kernel (taps out of an LDS-staged box) when the
-                              // box fits; bits 2 / 4 / 8: timing ablations (no second phase / no taps / no box DMA)
+                              // box fits
 extern "C" int mi_debug_set_cubic_box(int on) { g_cubic_box = on; return MI_OK; }
-bool launch_cubic_box(const float *in, float *out, const int shape[3], const int oshape[3], const double *mat, int mode, double cval, int npad, hipStream_t s, int *rc, int dbg);   // cubic_fast.hip
+bool launch_cubic_box(const float *in, float *out, const int shape[3], const int oshape[3], const double *mat, int mode, double cval, int npad, hipStream_t s, int *rc);   // cubic_fast.hip
 bool launch_cubic_mapbox(const float *in, const void *coords, int coords_f64, float *out, const int shape[3], const int oshape[3], int mode, double cval, int npad,
-                         hipStream_t s, int *rc, int dbg);   // cubic_fast.hip
+                         hipStream_t s, int *rc);   // cubic_fast.hip
 Knob g_resample_fast{1};      // test hook: 0 = the r3 separable resampling passes for diagonal order-3 transforms
 extern "C" int mi_debug_set_resample_fast(int on) { g_resample_fast = on; return MI_OK; }
 int launch_resample_x_lds(const float *in, float *out, const AxisTaps *tabx, long long nrows, int ox, int nx, float cval, hipStream_t s);          // cubic_fast.hip
@@ -1990,8 +1990,7 @@ using namespace mi;
 static mi::Knob g_interp_generic{0};   // test hook: 1 = always use the generic double kernels
 static mi::Knob g_spline_gain_first{1};     // test hook: 0 = the one-thread-per-line kernel applies the gain with its last store
 extern "C" int mi_debug_set_spline_gain_first(int k) { g_spline_gain_first = k; return MI_OK; }
-static mi::Knob g_spline_threads{65536};   // threads the blocked prefilter aims for
-extern "C" int mi_debug_set_spline_threads(int k) { g_spline_threads = k; return MI_OK; }
+constexpr int64_t kSplineThreads = 65536;   // threads the blocked prefilter aims for
 static mi::Knob g_spline_chunk{0};     // test hook: -1 = never the blocked prefilter, > 0 = force it with this minimum chunk length
 extern "C" int mi_debug_set_spline_chunk(int k) { g_spline_chunk = k; return MI_OK; }
 static mi::Knob g_spline_rows_off{0};  // test hook: 1 = one thread per line also for contiguous lines
@@ -2150,7 +2149,7 @@ static int64_t spline_chunk_len(const mi_array *a, int axis, int order, int spli
           (nlines < 32768 || g_spline_chunk > 0)))
         return 0;
     // as many chunks as it takes to get ~64k threads, at least min_chunk samples each
-    int64_t nch = (g_spline_threads + nlines - 1) / nlines;
+    int64_t nch = (kSplineThreads + nlines - 1) / nlines;
     if (nch > n / min_chunk) nch = n / min_chunk;
     return nch >= 2 ? (n + nch - 1) / nch : 0;
 }
@@ -2434,7 +2433,7 @@ int mi_spline_map_coordinates(const mi_array *coef, const mi_array *coords, cons
         if (g_cubic_box && g.pad == 0 && out->ndim == 3) {
             const int shp[3] = {(int)g.shape[0], (int)g.shape[1], (int)g.shape[2]}, osh[3] = {(int)out->shape[0], (int)out->shape[1], (int)out->shape[2]};
             int mrc = MI_OK;
-            if (launch_cubic_mapbox((const float *)coef->data, coords->data, coords->dtype == MI_F64, (float *)out->data, shp, osh, mode, cval, npad, s, &mrc, g_cubic_box))
+            if (launch_cubic_mapbox((const float *)coef->data, coords->data, coords->dtype == MI_F64, (float *)out->data, shp, osh, mode, cval, npad, s, &mrc))
                 return mrc;
         }
         note_kernel("mi::cubic3_f32_kernel (order-3 map_coordinates on float32 coefficients: 16 x 16-byte gathers per voxel)");
@@ -2588,7 +2587,7 @@ int mi_spline_affine_transform(const mi_array *coef, const mi_array *out, const 
             // r5: all three axes coupled (small rotations about a general axis): taps out of an LDS-staged box (csrc/cubic_fast.hip)
             if (g_cubic_box && g.pad == 0) {
                 const int shp[3] = {(int)g.shape[0], (int)g.shape[1], (int)g.shape[2]}, osh[3] = {(int)g.oshape[0], (int)g.oshape[1], (int)g.oshape[2]};
-                if (launch_cubic_box((const float *)coef->data, (float *)out->data, shp, osh, g.mat, mode, cval, npad, s, &zrc, g_cubic_box)) return zrc;
+                if (launch_cubic_box((const float *)coef->data, (float *)out->data, shp, osh, g.mat, mode, cval, npad, s, &zrc)) return zrc;
             }
         }
         note_kernel(diagonal ? "mi::cubic3_diag_f32_kernel (order-3 affine on float32 coefficients, diagonal matrix: tabulated taps)"

@@ -482,7 +482,6 @@ struct LdsAffineParams {
     // box origin in closed form: the minimum of an affine coordinate over the tile is its value at the tile's first
     // voxel plus cmin[a] = sum_j min(0, m[a][j] (T_j - 1))
     double cmin[3];
-    int dbg;                 // tuning ablations (0 in production): 1 no box DMA, 2 no interpolation (stores only), 4 no stores
 };
 
 constexpr int kLdsRoundsMax = 16;                           // staging rounds of 512 chunks (8 KiB) a box can take
@@ -596,14 +595,14 @@ affine3d_lds_kernel(const float *__restrict__ in, float *__restrict__ out, const
         const unsigned base = (unsigned)((b0[0] * p.ny + b0[1]) * p.nx + b0[2]) * 4u;
 #pragma unroll
         for (int j = 0; j < kLdsRoundsMax; j++)
-            if (j < rounds && !(q.dbg & 1)) dma_16s(rin, rel[j], base, (unsigned)((wave << 6) + (j << 9)) * 16u);
+            if (j < rounds) dma_16s(rin, rel[j], base, (unsigned)((wave << 6) + (j << 9)) * 16u);
     } else {
         int c4 = c40, ry = ry0, rz = rz0;
         for (int j = 0; j < rounds; j++) {
             const int sz_ = b0[0] + rz, sy_ = b0[1] + ry, sx_ = b0[2] + 4 * c4;
             const bool ok = tid + (j << 9) < q.nchunks && sz_ < p.nz && sy_ < p.ny && sx_ < p.nx;
             const unsigned voff = ok ? (unsigned)((sz_ * p.ny + sy_) * p.nx + sx_) * 4u : 0x80000000u;
-            if (!(q.dbg & 1)) dma_16(rin, voff, (unsigned)((wave << 6) + (j << 9)) * 16u);
+            dma_16(rin, voff, (unsigned)((wave << 6) + (j << 9)) * 16u);
             c4 += q.dc4; ry += q.dry; rz += q.drz;
             if (c4 >= cpr) { c4 -= cpr; ry++; }
             if (ry >= q.by) { ry -= q.by; rz++; }
@@ -624,7 +623,6 @@ affine3d_lds_kernel(const float *__restrict__ in, float *__restrict__ out, const
 #pragma unroll 1
     for (int bt = 0; bt < 2; bt++) {
         float r[4] = {0.f, 0.f, 0.f, 0.f};
-        if (!(q.dbg & 2))
 #pragma unroll
         for (int kk = 0; kk < 4; kk++) {
             const int k = 8 * wz + 4 * bt + kk;
@@ -651,7 +649,6 @@ affine3d_lds_kernel(const float *__restrict__ in, float *__restrict__ out, const
             }
             r[kk] = finish<float>(t, (float)p.cval);
         }
-        if (q.dbg & 4) continue;
         if (wide) {
 #pragma unroll
             for (int kk = 0; kk < 4; kk++) tile[kk * 64 + lane] = r[kk];
@@ -679,7 +676,6 @@ affine3d_lds_kernel(const float *__restrict__ in, float *__restrict__ out, const
 }
 
 extern "C" int mi_debug_set_affine_box_kib(int k) { g_affine_box_kib = k; return MI_OK; }
-Knob g_affine_dbg{0};     // tuning ablations of affine3d_lds_kernel, see LdsAffineParams::dbg
 Knob g_affine_gz{0};      // test hook: workgroups along z of affine3d_lds_kernel (0 = auto; the number of z tiles = one tile per workgroup)
 
 // box dimensions of a TZ x TY x TX output tile under the matrix (upper bound from |M|); returns the number of floats,
@@ -718,7 +714,6 @@ static long long lds_affine_plan(const FastInterpParams &p, int tx, int ty, LdsA
         for (int j = 0; j < 3; j++) { const double e = p.m[4 * a + j] * T[j]; if (e < 0.0) c += e; }
         q->cmin[a] = c;
     }
-    q->dbg = g_affine_dbg;
     return floats;
 }
 
@@ -1172,7 +1167,6 @@ struct ZStreamParams {
     double cmin_y, cmin_x;   // minimum of cR / cx over a tile relative to its first voxel (see LdsAffineParams::cmin)
     int zc, nzc;             // output planes per chunk, chunks
     int ntx, nty;            // tiles along x / R
-    int dbg;
 };
 
 // r4b: the staged window of a plane is SHEARED.  A tile of TY x 64 output voxels reads, in one input plane, a parallelogram
@@ -1246,7 +1240,7 @@ __device__ __forceinline__ ZSplit zs_split(double m0, double m3, int z, int nz)
 template <int NT>
 __device__ __forceinline__ void zs_ensure_rect(const float *in, int vol_bytes, int pl, int nz, int &rlo, int &rhi,
                                           const unsigned (&rel)[kZsRoundsMax], int rounds, unsigned plane_b, unsigned org_b,
-                                          unsigned slot_bytes, int wave, bool off)
+                                          unsigned slot_bytes, int wave)
 {
     if (pl < 0 || pl >= nz) return;
     if (pl >= rlo && pl <= rhi) return;
@@ -1259,7 +1253,7 @@ __device__ __forceinline__ void zs_ensure_rect(const float *in, int vol_bytes, i
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)sl * slot_bytes + (unsigned)(wave << 6) * 16u);
 #pragma unroll
     for (int j = 0; j < kZsRoundsMax; j++)
-        if (j < rounds && !off) dma_16s(rin, rel[j], base, __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(j * NT) * 16u));
+        if (j < rounds) dma_16s(rin, rel[j], base, __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(j * NT) * 16u));
 }
 
 template <int TY, int SAX>
@@ -1279,7 +1273,7 @@ affine3d_zrect_kernel(const float *__restrict__ in, float *__restrict__ out, con
     // then holds runs of x-neighbouring tiles, whose rectangles overlap, of the same chunk
     const int total = q.ntx * q.nty * q.nzc;
     int t = blockIdx.x;
-    if ((total & 7) == 0 && !(q.dbg & 64)) t = (t & 7) * (total >> 3) + (t >> 3);
+    if ((total & 7) == 0) t = (t & 7) * (total >> 3) + (t >> 3);
     const int tx_i = t % q.ntx, ty_i = (t / q.ntx) % q.nty, zc_i = t / (q.ntx * q.nty);
     const int x0 = tx_i * 64, y0 = ty_i * TY;
     const int zs = zc_i * q.zc, ze = min(zs + q.zc, q.oS);
@@ -1336,8 +1330,7 @@ affine3d_zrect_kernel(const float *__restrict__ in, float *__restrict__ out, con
     const int nz_ = q.nS, vol_bytes = q.vol_bytes;
     const double m0_ = q.mS, m3_ = q.offS;
     constexpr bool s0 = SAX == 0;
-    const bool no_dma = (q.dbg & 1) != 0;
-#define ZS_ENSURE(PL) zs_ensure_rect<NT>(in, vol_bytes, (PL), nz_, rlo, rhi, rel, rounds, plane_b, org_b, slot_bytes, wave, no_dma)
+#define ZS_ENSURE(PL) zs_ensure_rect<NT>(in, vol_bytes, (PL), nz_, rlo, rhi, rel, rounds, plane_b, org_b, slot_bytes, wave)
     ZSplit cur = zs_split(m0_, m3_, zs, nz_);
     if (cur.in) { ZS_ENSURE(cur.i0); ZS_ENSURE(cur.i0 + 1); }
     const float cval = (float)q.cval;
@@ -1358,7 +1351,7 @@ affine3d_zrect_kernel(const float *__restrict__ in, float *__restrict__ out, con
             if (nxt.in) { ZS_ENSURE(nxt.i0); ZS_ENSURE(nxt.i0 + 1); }
         }
         float r[8];
-        if (cur.in && !(q.dbg & 2)) {
+        if (cur.in) {
             const char *lo_p = smem_zs + (unsigned)(cur.i0 & 3) * slot_bytes;
             const char *hi_p = smem_zs + (unsigned)((cur.i0 + 1) & 3) * slot_bytes;
 #pragma unroll
@@ -1382,25 +1375,23 @@ affine3d_zrect_kernel(const float *__restrict__ in, float *__restrict__ out, con
 #pragma unroll
             for (int k = 0; k < 8; k++) r[k] = cval;
         }
-        if (!(q.dbg & 4)) {
-            if (wide) {
+        if (wide) {
 #pragma unroll
-                for (int k = 0; k < 8; k++) tile[k * 64 + lane] = r[k];
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                const int i = lane >> 4, c = lane & 15;
+            for (int k = 0; k < 8; k++) tile[k * 64 + lane] = r[k];
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            const int i = lane >> 4, c = lane & 15;
 #pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    const f32x4n v = *reinterpret_cast<const f32x4n *>(tile + (4 * h + i) * 64 + 4 * c);
-                    __builtin_nontemporal_store(v, reinterpret_cast<f32x4n *>(out + (size_t)z * q.out_sS + (size_t)(y0 + 8 * wave + 4 * h + i) * q.out_sR + x0 + 4 * c));
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the tile is rewritten next step
-            } else {
-                const int x = x0 + lane;
+            for (int h = 0; h < 2; h++) {
+                const f32x4n v = *reinterpret_cast<const f32x4n *>(tile + (4 * h + i) * 64 + 4 * c);
+                __builtin_nontemporal_store(v, reinterpret_cast<f32x4n *>(out + (size_t)z * q.out_sS + (size_t)(y0 + 8 * wave + 4 * h + i) * q.out_sR + x0 + 4 * c));
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the tile is rewritten next step
+        } else {
+            const int x = x0 + lane;
 #pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const int y = y0 + 8 * wave + k;
-                    if (x < q.ox && y < q.oR) __builtin_nontemporal_store(r[k], out + (size_t)z * q.out_sS + (size_t)y * q.out_sR + x);
-                }
+            for (int k = 0; k < 8; k++) {
+                const int y = y0 + 8 * wave + k;
+                if (x < q.ox && y < q.oR) __builtin_nontemporal_store(r[k], out + (size_t)z * q.out_sS + (size_t)y * q.out_sR + x);
             }
         }
         cur = nxt;
@@ -1416,7 +1407,7 @@ affine3d_zrect_kernel(const float *__restrict__ in, float *__restrict__ out, con
 template <int NT>
 __device__ __forceinline__ void zs_ensure(const float *in, int vol_bytes, int pl, int nz, int &rlo, int &rhi,
                                           const unsigned (&rel)[kZsRoundsMax], int rounds, unsigned plane_b, unsigned org_b,
-                                          unsigned slot_bytes, int wave, bool off, int nslots)
+                                          unsigned slot_bytes, int wave, int nslots)
 {
     if (pl < 0 || pl >= nz) return;
     if (pl >= rlo && pl <= rhi) return;
@@ -1429,7 +1420,7 @@ __device__ __forceinline__ void zs_ensure(const float *in, int vol_bytes, int pl
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)sl * slot_bytes + (unsigned)(wave << 6) * 16u);
 #pragma unroll
     for (int j = 0; j < kZsRoundsMax; j++)
-        if (j < rounds && !off) dma_16s(rin, rel[j], base, __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(j * NT) * 16u));
+        if (j < rounds) dma_16s(rin, rel[j], base, __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(j * NT) * 16u));
 }
 
 // SHEAR = true is what is instantiated (row starts of their own); the rectangle form lives in affine3d_zrect_kernel above.
@@ -1451,7 +1442,7 @@ affine3d_zstream_kernel(const float *__restrict__ in, float *__restrict__ out, c
     // then holds runs of x-neighbouring tiles, whose windows overlap, of the same chunk
     const int total = q.ntx * q.nty * q.nzc;
     int t = blockIdx.x;
-    if ((total & 7) == 0 && !(q.dbg & 64)) t = (t & 7) * (total >> 3) + (t >> 3);
+    if ((total & 7) == 0) t = (t & 7) * (total >> 3) + (t >> 3);
     const int tx_i = t % q.ntx, ty_i = (t / q.ntx) % q.nty, zc_i = t / (q.ntx * q.nty);
     const int x0 = tx_i * 64, y0 = ty_i * TY;
     const int zs = zc_i * q.zc, ze = min(zs + q.zc, q.oS);
@@ -1542,8 +1533,7 @@ affine3d_zstream_kernel(const float *__restrict__ in, float *__restrict__ out, c
     const int nz_ = q.nS, vol_bytes = q.vol_bytes;
     const double m0_ = q.mS, m3_ = q.offS;
     constexpr bool s0 = SAX == 0;
-    const bool no_dma = (q.dbg & 1) != 0;
-#define ZS_ENSURE(PL) zs_ensure<NT>(in, vol_bytes, (PL), nz_, rlo, rhi, rel, rounds, plane_b, org_b, slot_bytes, wave, no_dma, NS)
+#define ZS_ENSURE(PL) zs_ensure<NT>(in, vol_bytes, (PL), nz_, rlo, rhi, rel, rounds, plane_b, org_b, slot_bytes, wave, NS)
     auto slot_of = [&](int pl) { return (unsigned)(NS == 4 ? (pl & 3) : (pl % 3 + 3) % 3); };
     ZSplit cur = zs_split(m0_, m3_, zs, nz_);
     if (cur.in) { ZS_ENSURE(cur.i0); ZS_ENSURE(cur.i0 + 1); }
@@ -1580,7 +1570,7 @@ affine3d_zstream_kernel(const float *__restrict__ in, float *__restrict__ out, c
             }
         }
         float r[8];
-        if (cur.in && !(q.dbg & 2) && any_bad) {
+        if (cur.in && any_bad) {
             // some voxel of this wave is not held by the window: the same blend with a per-voxel choice of the source
             const char *lo_p = smem_zs + slot_of(cur.i0) * slot_bytes;
             const char *hi_p = smem_zs + slot_of(cur.i0 + 1) * slot_bytes;
@@ -1611,7 +1601,7 @@ affine3d_zstream_kernel(const float *__restrict__ in, float *__restrict__ out, c
                 t.outside = !((inmask >> k) & 1u);
                 r[k] = finish<float>(t, cval);
             }
-        } else if (cur.in && !(q.dbg & 2)) {
+        } else if (cur.in) {
             const char *lo_p = smem_zs + slot_of(cur.i0) * slot_bytes;
             const char *hi_p = smem_zs + slot_of(cur.i0 + 1) * slot_bytes;
 #pragma unroll
@@ -1636,25 +1626,23 @@ affine3d_zstream_kernel(const float *__restrict__ in, float *__restrict__ out, c
 #pragma unroll
             for (int k = 0; k < 8; k++) r[k] = cval;
         }
-        if (!(q.dbg & 4)) {
-            if (wide) {
+        if (wide) {
 #pragma unroll
-                for (int k = 0; k < 8; k++) tile[k * 64 + lane] = r[k];
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                const int i = lane >> 4, c = lane & 15;
+            for (int k = 0; k < 8; k++) tile[k * 64 + lane] = r[k];
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            const int i = lane >> 4, c = lane & 15;
 #pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    const f32x4n v = *reinterpret_cast<const f32x4n *>(tile + (4 * h + i) * 64 + 4 * c);
-                    __builtin_nontemporal_store(v, reinterpret_cast<f32x4n *>(out + (size_t)z * q.out_sS + (size_t)(y0 + 8 * wave + 4 * h + i) * q.out_sR + x0 + 4 * c));
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the tile is rewritten next step
-            } else {
-                const int x = x0 + lane;
+            for (int h = 0; h < 2; h++) {
+                const f32x4n v = *reinterpret_cast<const f32x4n *>(tile + (4 * h + i) * 64 + 4 * c);
+                __builtin_nontemporal_store(v, reinterpret_cast<f32x4n *>(out + (size_t)z * q.out_sS + (size_t)(y0 + 8 * wave + 4 * h + i) * q.out_sR + x0 + 4 * c));
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the tile is rewritten next step
+        } else {
+            const int x = x0 + lane;
 #pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const int y = y0 + 8 * wave + k;
-                    if (x < q.ox && y < q.oR) __builtin_nontemporal_store(r[k], out + (size_t)z * q.out_sS + (size_t)y * q.out_sR + x);
-                }
+            for (int k = 0; k < 8; k++) {
+                const int y = y0 + 8 * wave + k;
+                if (x < q.ox && y < q.oR) __builtin_nontemporal_store(r[k], out + (size_t)z * q.out_sS + (size_t)y * q.out_sR + x);
             }
         }
         if (late0 >= 0 || late1 >= 0) {
@@ -1797,7 +1785,6 @@ static bool zstream_plan(const FastInterpParams &p, int S, ZStreamParams *q)
     q->cmin_x = (e[2] < 0.0 ? e[2] : 0.0) + (e[3] < 0.0 ? e[3] : 0.0);
     q->ntx = (p.ox + 63) / 64;
     q->nty = (q->oR + TY - 1) / TY;
-    q->dbg = g_affine_dbg;
     return true;
 }
 
@@ -1871,7 +1858,7 @@ template <int V> struct MzGeo {
 struct MapZParams {
     FastInterpParams f;
     int zc, nzc, ntx, nty;
-    int dbg;                 // 1 = no DMA, 2 = every step takes the L1 gathers, 4 = no stores, 8 = no interpolation (timing / test aids)
+    int gather_all;          // test hook (mi_debug_set_map_zstream(2)): every step takes the L1 gathers
 };
 
 // wave-wide minimum / maximum of a float, result as a wave-uniform scalar: four DPP row shifts inside each row of 16 lanes
@@ -1982,7 +1969,7 @@ map_coords3d_zstream_kernel(const float *__restrict__ in, const float *__restric
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int total = q.ntx * q.nty * q.nzc;
     int t = blockIdx.x;
-    if ((total & 7) == 0 && !(q.dbg & 64)) t = (t & 7) * (total >> 3) + (t >> 3);          // x-neighbouring tiles on one XCD
+    if ((total & 7) == 0) t = (t & 7) * (total >> 3) + (t >> 3);          // x-neighbouring tiles on one XCD
     const int tx_i = t % q.ntx, ty_i = (t / q.ntx) % q.nty, zc_i = t / (q.ntx * q.nty);
     const int x0 = tx_i * 64, y0 = ty_i * TY;
     const int zs = zc_i * q.zc, ze = min(zs + q.zc, oz);
@@ -2044,7 +2031,7 @@ map_coords3d_zstream_kernel(const float *__restrict__ in, const float *__restric
         const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(pl & 3) * (unsigned)kMzSlotBytes + (unsigned)(wave << 6) * 16u);
 #pragma unroll
         for (int j = 0; j < kRounds; j++)
-            if (!(q.dbg & 1)) dma_16s(rin, rel[j], base, __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(j * NT) * 16u));
+            dma_16s(rin, rel[j], base, __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(j * NT) * 16u));
     };
 
     // ---- phase A of a plane: raw coordinates -> integer parts / weights (into `st`) + the workgroup's bounding box of the
@@ -2137,7 +2124,7 @@ map_coords3d_zstream_kernel(const float *__restrict__ in, const float *__restric
     // ---- phase B: where do this plane's taps come from?  Returns 0 = LDS, planes fetched now; 1 = LDS, planes fetched after
     // the current plane has been read (re-centred rectangle, or its planes would land on slots in use); 2 = L1 gathers
     auto place = [&](int cur_zlo, int cur_zhi, bool cur_lds) {
-        if (q.dbg & 2) return 2;
+        if (q.gather_all) return 2;
         const int nyy = need_hi[1] + 2 - need_lo[1], nxx = need_hi[2] + 2 - need_lo[2], nzz = need_hi[0] + 2 - need_lo[0];
         if (nyy > RY || nxx > P - 3 || nzz > 4) return 2;
         const bool covered = need_lo[1] >= org_y && need_hi[1] + 1 < org_y + RY && need_lo[2] >= org_x && need_hi[2] + 1 < org_x + P;
@@ -2249,10 +2236,7 @@ map_coords3d_zstream_kernel(const float *__restrict__ in, const float *__restric
         }
         // ---- interpolate plane z
         float r[V];
-        if (q.dbg & 8) {
-#pragma unroll
-            for (int k = 0; k < V; k++) r[k] = cur.wz[k] + (float)cur.a[k];
-        } else if (CORNER && cur.lds && __builtin_amdgcn_ballot_w64(cur.bad != 0) != 0) {
+        if (CORNER && cur.lds && __builtin_amdgcn_ballot_w64(cur.bad != 0) != 0) {
             // some voxel of this wave verifies to "not staged": the same loop with a per-voxel choice of the source
             const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void *)in, 0, vol_bytes, 0x00020000);
 #pragma unroll
@@ -2309,12 +2293,7 @@ map_coords3d_zstream_kernel(const float *__restrict__ in, const float *__restric
                 for (int kk = 0; kk < 4; kk++) r[4 * h + kk] = finish<float>(t[kk], cval);
             }
         }
-        if (q.dbg & 4) {
-            float sum = 0.f;
-#pragma unroll
-            for (int k = 0; k < V; k++) sum += r[k];
-            if (sum == 1.2345e-30f) out[0] = r[0];                                      // keeps the work alive
-        } else if (wide) {
+        if (wide) {
 #pragma unroll
             for (int k = 0; k < V; k++) my_stage[k * 64 + lane] = r[k];
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -2480,8 +2459,7 @@ template <bool CORNER, int V, int DEEP>
 static int launch_map_zstream_as(const float *in, const float *coords, float *out, MapZParams &q, int tiles, hipStream_t s)
 {
     using G = MzGeo<V>;
-    size_t lds = 4 * (size_t)kMzSlotBytes + (size_t)G::NW * G::STG + (CORNER ? 0 : 64);
-    if (g_affine_dbg & 32) lds = 96 * 1024;                 // occupancy experiment: one workgroup per CU
+    const size_t lds = 4 * (size_t)kMzSlotBytes + (size_t)G::NW * G::STG + (CORNER ? 0 : 64);
     static PerDeviceOnce attr_done;
     if (!attr_done) {
         MI_HIP(hipFuncSetAttribute((const void *)map_coords3d_zstream_kernel<CORNER, V, DEEP>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
@@ -2506,7 +2484,7 @@ static int launch_map_zstream(const float *in, const float *coords, float *out, 
     nzc = std::max(1, std::min(nzc, (p.oz + 15) / 16));
     q.zc = (p.oz + nzc - 1) / nzc;
     q.nzc = (p.oz + q.zc - 1) / q.zc;
-    q.dbg = (g_affine_dbg & (13 | 64)) | (g_map_zstream == 2 ? 2 : 0);
+    q.gather_all = g_map_zstream == 2;
     if (g_map_zstream == 3) return launch_map_zstream_as<false, 8, 1>(in, coords, out, q, tiles, s);
     switch ((int)g_map_zvariant) {
     case 81: return launch_map_zstream_as<true, 8, 1>(in, coords, out, q, tiles, s);
@@ -2701,7 +2679,6 @@ int affine_transform_fast(const mi_array *in, const mi_array *out, const double 
 }  // namespace mi
 
 extern "C" int mi_debug_set_interp_c1(int k) { mi::g_interp_c1 = k; return MI_OK; }
-extern "C" int mi_debug_set_affine_dbg(int k) { mi::g_affine_dbg = k; return MI_OK; }
 extern "C" int mi_debug_set_affine_gz(int k) { mi::g_affine_gz = k; return MI_OK; }
 extern "C" int mi_debug_set_affine_rowblend(int k) { mi::g_affine_rowblend = k; return MI_OK; }
 extern "C" int mi_debug_set_map_zstream(int k) { mi::g_map_zstream = k; return MI_OK; }

@@ -1017,7 +1017,6 @@ bool long_aniso_pair(int w, int wzn)
 
 Knob g_stream_nt{-1};                  // long_common.hpp
 static mi::Knob g_long_zchunks{0};     // test hook: number of z chunks (0 = cost model)
-static mi::Knob g_long_same{1};        // test hook: 0 = always the reloading variant
 
 // Fused long-kernel path: cubic odd W in 11..17 (9 behind the test hook), origins on y / z allowed, no constant mode.
 // Returns MI_ERR_UNSUPPORTED when the request is outside that (the caller runs the streaming passes).
@@ -1122,7 +1121,7 @@ int run_sep3d_long(const float *in, float *out, int nz, int ny, int nx, int w, i
 #undef MI_LONG_RAGGED
         return MI_ERR_UNSUPPORTED;
     }
-    bool same = g_long_same != 0;
+    bool same = true;
     for (int k = 0; k < w; k++) same = same && wx[k] == wy[k] && wy[k] == wz[k];
 #define MI_LONG_CASE(N)                                                                                   \
     case N:                                                                                               \
@@ -1139,6 +1138,5 @@ int run_sep3d_long(const float *in, float *out, int nz, int ny, int nx, int w, i
 
 extern "C" int mi_debug_set_stream_nt(int k) { mi::g_stream_nt = k; return MI_OK; }
 extern "C" int mi_debug_set_long_zchunks(int n) { mi::g_long_zchunks = n; return MI_OK; }
-extern "C" int mi_debug_set_long_same(int n) { mi::g_long_same = n; return MI_OK; }
 extern "C" int mi_debug_set_long_rows(int k) { mi::g_long_rows = k; return MI_OK; }
 extern "C" int mi_debug_set_long_const0(int k) { mi::g_long_const0 = k; return MI_OK; }

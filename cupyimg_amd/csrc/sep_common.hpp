@@ -32,8 +32,9 @@ struct Sep3dParams {
     // zb0 = 0, zn0 = nz, nzc0 = nzc).  Boundary handling always refers to nz.
     int zb0, zn0, zb1, zn1, nzc0;
     float wx[kMaxTaps], wyv[kMaxTaps], wz[kMaxTaps];
-    int dbg;                // tuning ablations (0 in production): 1 no x/z math, 2 no stores, 4 no loads, 8 no y math
-    int zrev;               // lean kernel: odd z chunks stream DOWNWARDS (see sep3d_lean_kernel)
+    // always 0, read by sep3d_ws_kernel only: without its four uniform tests on this field most of that kernel's instances
+    // compile to more registers and <7,7> / <9,7> spill to scratch (the lean kernel has no such field any more)
+    int dbg;
 };
 
 __device__ __forceinline__ void chunk_planes(const Sep3dParams &p, int zci, int *zs, int *ze)

@@ -359,18 +359,6 @@ static int launch_runs_f32(const float *in, float *out, RunsF32Params &p, bool i
     return MI_OK;
 }
 
-// Round 1 issued a pass in launches of at most 1000 waves because larger launches produced wrong samples; the
-// cause was the store-data hazard described at buffer_store_b128_soff() (sep_common.hpp), not the launch size.
-// The slice hook stays for tests (0 = one launch, the default).
-mi::Knob g_xcd_swizzle{2};               // test hook: 0 = plain workgroup order, 1 = always XCD-contiguous, 2 = auto
-extern "C" int mi_debug_set_xcd_swizzle(int k) { g_xcd_swizzle = k; return MI_OK; }
-static mi::Knob g_stream_wpb{4};             // test hook: waves per workgroup (1, 2 or 4)
-extern "C" int mi_debug_set_stream_wpb(int n) { g_stream_wpb = n; return MI_OK; }
-static mi::Knob g_stream_slice{0};           // test hook: waves per launch of a pass (0 = one launch)
-extern "C" int mi_debug_set_stream_slice(int n) { g_stream_slice = n; return MI_OK; }
-static mi::Knob g_stream_min_chunk{16};      // test hook: shortest chunk the planner may choose
-extern "C" int mi_debug_set_stream_min_chunk(int n) { g_stream_min_chunk = n; return MI_OK; }
-
 template <int WX, int WA, int OP = SP_CORR>
 static int launch_stream(const float *in, float *out, StreamParams &p, hipStream_t s)
 {
@@ -386,7 +374,7 @@ static int launch_stream(const float *in, float *out, StreamParams &p, hipStream
         double best = 1e300;
         for (int c = 1; c <= nA && c <= 1024; c++) {
             const int chunk = (nA + c - 1) / c;
-            if (c > 1 && chunk < g_stream_min_chunk) break;
+            if (c > 1 && chunk < 16) break;
             const int real = (nA + chunk - 1) / chunk;
             const double rounds = std::max(1.0, (double)nlines * real / 4096.0);
             const double cost = rounds * (chunk + (WA - 1) + 4.0);
@@ -396,16 +384,12 @@ static int launch_stream(const float *in, float *out, StreamParams &p, hipStream
     p.chunk = (nA + nch - 1) / nch;
     p.nchunks = (nA + p.chunk - 1) / p.chunk;
     const int waves = nlines * p.nchunks;
-    const int slice = g_stream_slice > 0 ? (int)g_stream_slice : waves;
-    const int wpb = g_stream_wpb;
+    constexpr int wpb = 4;                    // waves per workgroup; the whole pass is one launch (wid_base = 0)
     p.wpb = wpb;
+    p.wid_base = 0;
     p.swz = xcd_swizzle_for((size_t)p.nx * p.ny * p.nz * 4);
-    for (int base = 0; base < waves; base += slice) {
-        p.wid_base = base;
-        const int n = std::min(slice, waves - base);
-        note_kernel("mi::stream_pass_kernel<%d,%d,%d,%d> grid=%d", WX, WA, DEPTH, (int)OP, (n + wpb - 1) / wpb);
-        hipLaunchKernelGGL((stream_pass_kernel<WX, WA, DEPTH, OP>), dim3((n + wpb - 1) / wpb), dim3(64 * wpb), 0, s, in, out, p);
-    }
+    note_kernel("mi::stream_pass_kernel<%d,%d,%d,%d> grid=%d", WX, WA, DEPTH, (int)OP, (waves + wpb - 1) / wpb);
+    hipLaunchKernelGGL((stream_pass_kernel<WX, WA, DEPTH, OP>), dim3((waves + wpb - 1) / wpb), dim3(64 * wpb), 0, s, in, out, p);
     MI_HIP(hipGetLastError());
     return MI_OK;
 }

@@ -34,21 +34,21 @@ struct StreamParams {
     // window pairs: xpair[q][2u], xpair[q][2u+1] = wx[2u - (B+q)%2], wx[2u + 1 - (B+q)%2]
     // for output parity q (B = window offset of tap 0, see xpass_hops); 0 outside the kernel
     float xpair[2][2 * (kStreamMaxTaps / 2 + 2)];
-    int wid_base;        // first wave index of this launch (a pass is issued in slices of waves)
-    int wpb;             // waves per workgroup of this launch
+    // stream_pass_kernel reads the next two as parameters although the host always passes 0 and 4: they stay so
+    // that its instances compile to the code they always had
+    int wid_base;        // first wave index of this launch (0: a pass is one launch)
+    int wpb;             // waves per workgroup of this launch (4)
     int swz;             // XCD-aware workgroup order (xcd_block())
 };
 
 // Workgroups are handed to the 8 XCDs round robin (workgroup i -> XCD i % 8), and every XCD has its own L2: with the
 // plain order, neighbouring chunks of an image -- which share their ramp rows -- land on different XCDs and each L2
 // fetches those rows from HBM again (measured 1.3-1.4x the algorithmic reads for 7-17-row windows).  This order gives
-// every XCD a contiguous run of workgroups.  g_xcd_swizzle: test hook (0 = plain order).
-extern Knob g_xcd_swizzle;        // 0 = plain order, 1 = always, 2 = auto
-// auto: arrays up to 128 MiB (4096^2 float32 +7 %, 8192^2 float32 +4 %; a 1 GiB image LOSES 7 %: eight distant streams
+// every XCD a contiguous run of workgroups, for arrays up to 128 MiB (4096^2 float32 +7 %, 8192^2 float32 +4 %; a 1 GiB image LOSES 7 %: eight distant streams
 // instead of one front moving through the DRAM pages)
 static inline int xcd_swizzle_for(size_t array_bytes)
 {
-    return g_xcd_swizzle == 1 || (g_xcd_swizzle == 2 && array_bytes <= ((size_t)128 << 20));
+    return array_bytes <= ((size_t)128 << 20);
 }
 __device__ __forceinline__ int xcd_block(int b, int nblocks, int enabled)
 {

@@ -1,8 +1,9 @@
 /* mi355img_debug.h -- test and tuning entry points of libmi355img.so.
  *
  * NOT part of the drop-in boundary (include/mi355img.h): nothing in the product path calls these; they exist so
- * that tests can force a particular kernel (to compare two device paths bit for bit), tuning sweeps can walk tile
- * shapes, and bench.py can name the kernel it timed.  The setters write process-wide knobs held as relaxed atomics
+ * that tests can force a particular kernel (to compare two device paths bit for bit), the A/B scripts of scripts/ can
+ * time a real alternative, and bench.py can name the kernel it timed.  A setter belongs here while a test, bench.py, the
+ * Python package or one of those scripts calls it; ablation flags and tuning overrides do not.  The setters write process-wide knobs held as relaxed atomics
  * (mi::Knob, csrc/common.hpp): flipping one while other threads dispatch is not a data race, but it does change
  * which kernel those threads' NEXT calls take -- keep them out of production code.  All return MI_OK.
  */
@@ -16,25 +17,13 @@ extern "C" {
 #endif
 
 /* ---- fused separable float32 kernels (csrc/separable3d.hip, sep3d_long.hip, stream3d.hip) */
-int mi_debug_set_sep3d_cfg(int cfg);          /* lean kernel tile shape variant (0 = cost model) */
-int mi_debug_set_sep3d_zchunks(int n);        /* number of z chunks (0 = cost model) */
-int mi_debug_set_sep3d_dbg(int flags);        /* ablations: 1 no x/z math, 2 no stores, 4 no loads, 8 no y math */
-int mi_debug_set_sep3d_kernel(int k);         /* 1 = always the general (ws) kernel */
-int mi_debug_set_sep3d_zrev(int on);          /* 0 = every z chunk streams upwards */
 int mi_debug_set_sep3d_image2d(int on);       /* 0 = images take the tiled volume kernel */
 int mi_debug_set_sep3d_long(int k);           /* 0 auto (9..17 taps, and 3..7 taps on large volumes with full tiles), 1 never the long kernel, 2 long kernel for all of 3..17 taps */
-int mi_debug_set_sep3d_box(int k);            /* no effect: the value is stored and read nowhere (no running-sum box kernel exists; kept for the ABI) */
 int mi_debug_set_sep3d_ragged(int k);         /* r5: 1 (default) the 3 / 5 / 7-tap kernel takes rows that are not a multiple of 4 floats, 0 refuse them (r6: the switch also covers the 9 .. 17-tap LDS-DMA kernel's ragged build) */
 int mi_debug_set_median27(int k);             /* r5: 1 (default) 3 x 3 x 3 medians of volumes on the shared-sort streaming kernel, 0 the per-voxel network */
 int mi_debug_set_long_const0(int k);          /* r5: 1 (default) constant mode with cval == 0 on the r3 long kernel, 0 the r2 kernel */
 int mi_debug_set_long_zchunks(int n);
-int mi_debug_set_long_same(int on);
 int mi_debug_set_long_rows(int k);            /* long kernel: 0 auto (r3 kernel), 1 the r2 instruction stream (kept for 9 / 13 / 17 taps as the comparator), 4 the r4 kernel with the y pass on the matrix cores (9 / 13 / 17 taps) */
-int mi_debug_set_stream_fused_max(int taps);
-int mi_debug_set_xcd_swizzle(int k);
-int mi_debug_set_stream_wpb(int n);
-int mi_debug_set_stream_slice(int n);
-int mi_debug_set_stream_min_chunk(int n);
 int mi_debug_set_minmax_f32_fused(int on);
 int mi_debug_stream_pass(const float *in, float *out, int nz, int ny, int nx, int axis, const float *wav, int wa,
                          int oa, int ma, const float *wxv, int wx, int mx, float cval, mi_stream stream);
@@ -79,10 +68,8 @@ int mi_debug_set_map_zvariant(int k);         /* its instance: 10 x voxels per t
 int mi_debug_set_affine_zstream(int k);       /* z-streaming affine kernel (axis 0 decoupled): 0 off, 1 auto, 32 / 64 tile height */
 int mi_debug_set_affine_zchunks(int k);       /* its z chunks (0 = planner) */
 int mi_debug_set_affine_box_kib(int k);       /* LDS-staged affine kernel: box budget per workgroup in KiB (0 = default 64; 36 = the r3 / r4 rule) */
-int mi_debug_set_affine_dbg(int k);           /* LDS-staged affine kernel ablations: 1 no box DMA, 2 no interpolation, 4 no stores (timing only) */
 int mi_debug_set_interp_c1(int k);            /* csrc/interp_fast.hip: 0 = round-2 order-1 constant-mode kernels, 1 = r3 (default), 2 = r3, narrow stores */
 int mi_debug_set_spline_gain_first(int on);
-int mi_debug_set_spline_threads(int n);
 int mi_debug_set_spline_chunk(int n);
 int mi_debug_set_spline_rows(int k);
 int mi_debug_set_cubic_separable(int on);
@@ -91,7 +78,7 @@ int mi_debug_set_spline_rows_lds(int on);     /* spline prefilter along the cont
 int mi_debug_set_spline_fast(int k);          /* r5 prefilter kernels (csrc/spline_fast.hip: one memory sweep per axis): 0 = never, 1 = volumes with >= 16384 lines (default), 2 = any line count */
 int mi_debug_set_cubic_rowblend(int on);      /* order-3 affine on float32 coefficients, x axis to itself: 0 = the gather kernel, 1 = the row-blend kernel (default) */
 int mi_debug_set_cubic_zstream(int on);       /* order-3 affine on float32 coefficients, axis 0 decoupled: 0 = the gather kernel, 1 = the z-streaming kernel (default), bits on top of 1: 2 = every wave on its gather path, 4 = no limit on the angle, 8 = grid-wrap / grid-constant too */
-int mi_debug_set_cubic_box(int on);           /* order-3 affine, all three axes coupled: 1 = taps out of an LDS-staged box when it fits (r5, default), 0 = the gather kernel; bits 2 / 4 / 8: timing ablations */
+int mi_debug_set_cubic_box(int on);           /* order-3 affine, all three axes coupled: 1 = taps out of an LDS-staged box when it fits (r5, default), 0 = the gather kernel */
 int mi_debug_set_resample_fast(int on);       /* diagonal order-3 transforms on volumes (zoom, shift): 1 = r5 passes (x from LDS-staged spans, z with the plane window in registers), 0 = r3 passes (bit-identical) */
 int mi_debug_set_cubic_zfactor(int on);       /* order-3 affine, stream axis decoupled: 1 = cubic3_zfactor_kernel (r5: in-plane values once per input plane; float32 rounding away from the gather kernel), 0 = cubic3_zstream_kernel (r4b: bit-identical to the gather kernel) */
 int mi_debug_set_stream_nt(int k);             /* non-temporal staging of rows no other workgroup reads (sep3d_long3 <= 9 taps, mm3f32_long, mm3u8_split <= 5): -1 by volume size (default), 0 never, 1 always */

@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage: scripts/pmc.sh <outdir-name> ; env CFG ZCH etc are passed to prof_one.py
+# usage: scripts/pmc.sh <outdir-name> ; env LONG LZCH etc are passed to prof_one.py
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$1

@@ -1,4 +1,4 @@
-"""Runs the headline op a few times (for rocprofv3).  env: CFG, ZCH, N, SIZE, REPS"""
+"""Runs the headline op a few times (for rocprofv3).  env: LONG, LZCH, N, SIZE, REPS"""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -10,10 +10,7 @@ from cupyimg_amd.scipy import ndimage as ndi
 n = int(os.environ.get("N", "512"))
 size = int(os.environ.get("SIZE", "5"))
 lib = _lib.load()
-lib.mi_debug_set_sep3d_cfg(int(os.environ.get("CFG", "0")))
-lib.mi_debug_set_sep3d_zchunks(int(os.environ.get("ZCH", "0")))
 lib.mi_debug_set_sep3d_long(int(os.environ.get("LONG", "0")))
-lib.mi_debug_set_sep3d_zrev(int(os.environ.get("ZREV", "1")))
 lib.mi_debug_set_long_zchunks(int(os.environ.get("LZCH", "0")))
 x = np.random.default_rng(0).standard_normal((n, n, n), dtype=np.float32)
 xd = ca.asarray(x)

@@ -1,6 +1,6 @@
-"""r3: phase ablations of affine3d_lds_kernel on config D' (mi_debug_set_affine_dbg: 1 no box DMA, 2 no interpolation,
-4 no stores) -- timing only, the results of an ablated run are meaningless."""
-import sys, time
+"""r3: workgroups-per-column sweep of affine3d_lds_kernel on config D' (the phase ablations this script also timed
+were removed from the kernel; their figures are in profiles/r3_affine_ablation.txt)."""
+import sys
 sys.path.insert(0, '.'); sys.path.insert(0, 'tests')
 import numpy as np, cupyimg_amd as ca
 from cupyimg_amd import _lib
@@ -20,8 +20,3 @@ for gz in (0, 64, 3, 6, 12, 24, 0):
     lib.mi_debug_set_affine_gz(gz)
     print("affine3d_lds workgroups along z = %d (0 auto, 64 = one tile each): %.1f us" % (gz, t(f)), flush=True)
 lib.mi_debug_set_affine_gz(0)
-for dbg in (0, 1, 2, 4, 3, 5, 6, 7, 0):
-    lib.mi_debug_set_affine_dbg(dbg)
-    print("affine3d_lds dbg=%d (1 no DMA, 2 no interpolation, 4 no stores): %.1f us" % (dbg, t(f)), flush=True)
-    time.sleep(0.2)
-lib.mi_debug_set_affine_dbg(0)

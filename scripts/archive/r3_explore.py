@@ -1,4 +1,4 @@
-"""Round-3 exploration sweep on the GPU box (not part of the product): copy ceilings, lean-kernel knobs and ablations,
+"""Round-3 exploration sweep on the GPU box (not part of the product): copy ceilings, the lean kernel at 3 / 5 / 7 taps,
 long-kernel chunking, sustained (60 launches) vs first-burst timings.   python scripts/r3_explore.py [what ...]"""
 import ctypes
 import os
@@ -49,24 +49,11 @@ if "copy" in what:
     time.sleep(1)
 
 if "lean" in what:
-    ref = None
+    lib.mi_debug_set_sep3d_long(1)        # the lean kernel also where the long kernel would be taken
     for size in (5, 3, 7):
-        for cfg, zch, zrev in [(0, 0, 1), (0, 0, 0), (8, 0, 1), (0, 4, 1), (0, 16, 1), (5, 4, 1), (5, 8, 1), (2, 0, 1), (1, 0, 1), (3, 0, 1)]:
-            if size != 5 and cfg not in (0, 5):
-                continue
-            lib.mi_debug_set_sep3d_cfg(cfg); lib.mi_debug_set_sep3d_zchunks(zch); lib.mi_debug_set_sep3d_zrev(zrev)
-            try:
-                t = timeit(lambda: ndi.uniform_filter(xd, size=size, output=out))
-            except Exception as e:
-                print("size", size, "cfg", cfg, "zch", zch, "failed", repr(e)[:100]); continue
-            show("lean size=%d cfg=%d zchunks=%d zrev=%d" % (size, cfg, zch, zrev), t)
-            time.sleep(0.3)
-        lib.mi_debug_set_sep3d_cfg(0); lib.mi_debug_set_sep3d_zchunks(0); lib.mi_debug_set_sep3d_zrev(1)
-    for dbg in (1, 2, 4, 8, 3, 6, 9, 11, 15):
-        lib.mi_debug_set_sep3d_dbg(dbg)
-        show("lean size=5 ablation dbg=%d (1 no xz math,2 no stores,4 no loads,8 no y)" % dbg, timeit(lambda: ndi.uniform_filter(xd, size=5, output=out)))
+        show("lean size=%d" % size, timeit(lambda: ndi.uniform_filter(xd, size=size, output=out)))
         time.sleep(0.3)
-    lib.mi_debug_set_sep3d_dbg(0)
+    lib.mi_debug_set_sep3d_long(0)
 
 if "long" in what:
     for sigma, zch in [(2.0, 0), (2.0, 2), (2.0, 8), (1.0, 0), (1.5, 0)]:

@@ -16,10 +16,10 @@ M, off = fs.affine_case(512)
 def run():
     ndi.affine_transform(xd, M, off, order=1, mode="constant", output=out)
 res = []
-for zs, zc, dbg in [(0, 0, 0), (32, 0, 0), (64, 0, 0), (32, 2, 0), (32, 8, 0), (64, 2, 0), (64, 8, 0), (64, 16, 0), (32, 0, 1), (32, 0, 2), (32, 0, 4), (32, 0, 6), (64, 0, 1), (64, 0, 2), (64, 0, 6)]:
-    lib.mi_debug_set_affine_zstream(zs); lib.mi_debug_set_affine_zchunks(zc); lib.mi_debug_set_affine_dbg(dbg)
+for zs, zc in [(0, 0), (32, 0), (64, 0), (32, 2), (32, 8), (64, 2), (64, 8), (64, 16)]:
+    lib.mi_debug_set_affine_zstream(zs); lib.mi_debug_set_affine_zchunks(zc)
     s, f = timeit(run, 40)
-    print(json.dumps({"zstream": zs, "zchunks": zc, "dbg": dbg, "us": round(s * 1e6, 1), "first_us": round(f * 1e6, 1), "frac": round(8 * 512**3 / s / 8e12, 4), "kernel": last_kernel()[:110]}), flush=True)
-lib.mi_debug_set_affine_zstream(1); lib.mi_debug_set_affine_zchunks(0); lib.mi_debug_set_affine_dbg(0)
+    print(json.dumps({"zstream": zs, "zchunks": zc, "us": round(s * 1e6, 1), "first_us": round(f * 1e6, 1), "frac": round(8 * 512**3 / s / 8e12, 4), "kernel": last_kernel()[:110]}), flush=True)
+lib.mi_debug_set_affine_zstream(1); lib.mi_debug_set_affine_zchunks(0)
 run()
 print("parity whole volume:", fs.whole_volume_affine(x, M, off, out.get()))
