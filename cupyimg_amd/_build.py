@@ -90,6 +90,7 @@ SOURCES = [
     ("threshold.hip", ["-ffp-contract=off"]),
     ("segment.hip", ["-ffp-contract=off"]),
     ("template.hip", ["-ffp-contract=off"]),
+    ("richardson_lucy.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function",
           "-I" + os.path.join(os.path.dirname(HERE), "include")]

@@ -166,6 +166,8 @@ SIGNATURES = {
     "mi_structure_products": [_arr, _arr, _i, _i, _i, _d, _vp],
     "mi_corner_response": [_arr, _arr, _arr, _i, _d, _d, _vp],
     "mi_match_template": [_arr, _arr, _arr, _i, _i, _d, _d, _d, _vp],
+    "mi_richardson_lucy_needs_scratch": [_arr, _i64p, _ip],
+    "mi_richardson_lucy_step": [_arr, _arr, _arr, _dp, _i64p, _d, _i, _i, _vp, _vp],
     "mi_select_work_bytes": [ctypes.c_int64, _i64p],
     "mi_select_count": [_arr, _arr, _i64p, _vp],
     "mi_select_write": [_arr, _arr, _arr, _i, _vp],

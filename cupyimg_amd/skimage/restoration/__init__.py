@@ -7,8 +7,9 @@ import numpy as np
 from ... import core, _lib
 from ...scipy.ndimage import _support as S
 from ..filters import _img_as_float
+from ._deconvolution import richardson_lucy
 
-__all__ = ["denoise_tv_chambolle"]
+__all__ = ["denoise_tv_chambolle", "richardson_lucy"]
 
 # Iterations queued between two reads of the state block.  A read costs one stream synchronisation and a 64-byte copy (tens
 # of microseconds); an iteration queued after the stop costs two launches that return at once (a few microseconds each).

@@ -803,6 +803,29 @@ int mi_corner_response(const mi_array *elems, const mi_array *out0, const mi_arr
 int mi_match_template(const mi_array *image, const mi_array *tmpl, const mi_array *out, int pad_input, int mode, double cval, double mean,
                       double ssd, mi_stream stream);
 
+/* One iteration of Richardson-Lucy deconvolution (skimage.restoration.richardson_lucy; cupyimg/skimage/restoration/
+ * deconvolution.py:356-416, where an iteration is two whole-array convolutions, a division, an optional where and a multiply;
+ * csrc/richardson_lucy.hip).
+ *   image, u_in, u_out: C-contiguous float32 or float64 arrays of one shape and dtype T, rank 1 to MI_MAX_NDIM (other dtypes:
+ *   MI_ERR_UNSUPPORTED with nothing queued; the caller converts); u_out overlaps neither of the others.  psf: the point spread
+ *   function, already rounded to T, as HOST doubles in C order, psf_shape[d] >= 1 samples along axis d (image.ndim entries).
+ * With s = psf_shape, per axis, and every sample outside the image a 0 that is multiplied and added like any other:
+ *     c[i]     = sum_k psf[k] * u_in[i + (s - 1) / 2 - k]      the taps in C order of the reversed PSF (t = s - 1 - k)
+ *     r[i]     = image[i] / c[i];   r[i] = 0 where use_epsilon and c[i] < T(filter_epsilon)
+ *     u_out[i] = u_in[i] * sum_j psf[j] * r[i - s / 2 + j]     the taps in C order of j
+ *     clip:      u_out > 1 -> 1, u_out < -1 -> -1
+ * Taps whose PSF value is 0.0 are skipped; every other product is formed and added in double from +0.0 and each sum is rounded
+ * once to T (mi_correlate_nd's rule without acc_f32); the division and the last product are single operations in T; nothing is
+ * guarded, NaN, infinities and a zero c propagate.
+ *   Ranks 2 and 3: rl_fused_kernel, one launch, u and r in LDS rings streamed along axis 0, r never in memory; PSFs whose rings
+ *   do not fit 64 KiB of LDS, the other ranks and mi_debug_set_richardson_lucy(1): rl_ratio_kernel + rl_update_kernel, two
+ *   launches with r in scratch_dev (image.size elements of T; NULL: the call takes and returns a block of the pool itself).
+ *   mi_richardson_lucy_needs_scratch says which of the two a call with this image and PSF shape takes now.
+ * Nothing synchronises and nothing is read by the host. */
+int mi_richardson_lucy_needs_scratch(const mi_array *image, const int64_t *psf_shape, int *needs_scratch);
+int mi_richardson_lucy_step(const mi_array *image, const mi_array *u_in, const mi_array *u_out, const double *psf, const int64_t *psf_shape,
+                            double filter_epsilon, int use_epsilon, int clip, void *scratch_dev, mi_stream stream);
+
 /* ------------------------------------------------------------------ */
 /* K5: interpolation, spline order 0 and 1                              */
 /* ------------------------------------------------------------------ */

@@ -100,7 +100,8 @@ int mi_debug_regionprops_launches(void);    /* csrc/regionprops.hip: kernel laun
 int mi_debug_set_threshold(int small_tiles, int force_generic);   /* csrc/threshold.hip: small_tiles = 1: win_fused_kernel works on tiles of 3 x 5 samples in chunks of 2 planes instead of the planner's, so that small arrays have seams along every axis; force_generic = 1: every mi_window_mean_std call takes win_generic_kernel (one thread per output) */
 int mi_debug_set_boundaries(int small_tiles, int force_generic);   /* csrc/segment.hip: small_tiles = 1: bd_tile_kernel works on boxes of 2 x 3 x 5 voxels (3 x 5 pixels) instead of the planner's, so that small arrays have seams along every axis; force_generic = 1: every mi_find_boundaries call takes bd_generic_kernel (one thread per voxel) */
 int mi_debug_set_match_template(int route);   /* csrc/template.hip: 0 = the planner (mt_fused_kernel, and mt_generic_kernel for what it refuses); 1 = every mi_match_template call takes mt_generic_kernel (one thread per output); 2 = mt_fused_kernel on tiles of 3 x 8 outputs (volumes: 2 x 3 x 8) with a staging budget of 4 KiB instead of 64, so that small arrays have seams along every axis and their templates are walked in slabs */
-int mi_debug_segment_launches(void);        /* csrc/segment.hip: kernel launches queued by its entry points since the library was loaded (a count, not a status) */
+int mi_debug_set_richardson_lucy(int route);   /* csrc/richardson_lucy.hip: 0 = the planner (rl_fused_kernel where it was measured faster, rl_ratio_kernel + rl_update_kernel otherwise and for what the fused kernel refuses); 1 = every mi_richardson_lucy_step call takes the two split kernels (one thread per voxel); 2 = rl_fused_kernel on tiles of 3 x 5 outputs in chunks of 3 planes with a staging budget of 16 KiB instead of 64, so that small arrays have seams along every tiled axis, several chunks and rings that wrap; 3 = rl_fused_kernel on the planner's tiles wherever its rings fit, whatever the planner's table of measured cases says (scripts/bench_richardson_lucy.py measures that table with it) */
+int mi_debug_segment_launches(void);       /* csrc/segment.hip: kernel launches queued by its entry points since the library was loaded (a count, not a status) */
 
 #ifdef __cplusplus
 }
