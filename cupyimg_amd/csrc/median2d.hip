@@ -134,10 +134,10 @@ int run_median3x3_u8(const uint8_t *in, uint8_t *out, int nz, int ny, int nx, in
 int run_median3x3_16(const mi_array *in, const mi_array *out, int mx, int my, double cval, hipStream_t s);                   // minmax_16.hip
 int run_median3x3_f64(const mi_array *in, const mi_array *out, int mx, int my, double cval, hipStream_t s);                  // stream_f64.hip
 
-// chunks along y: enough waves to fill the chip (256 CUs x 16 resident waves), chunks of at least 16 rows
+// chunks along y: enough waves to fill the chip once (kStreamResidentWaves), chunks of at least 16 rows
 static void median_chunks(int nlines, int ny, int *chunk, int *nchunks)
 {
-    int nch = (4096 + nlines - 1) / nlines;
+    int nch = (kStreamResidentWaves + nlines - 1) / nlines;
     if (nch > ny / 16) nch = ny / 16;
     if (nch < 1) nch = 1;
     *chunk = (ny + nch - 1) / nch;
@@ -155,31 +155,31 @@ extern "C" int mi_median3x3(const mi_array *in, const mi_array *out, const int m
     if ((rc = check_array(in, "in")) || (rc = check_array(out, "out"))) return rc;
     MI_REQUIRE(mode, MI_ERR_INVALID_ARG, "NULL argument");
     MI_REQUIRE(same_shape(in, out), MI_ERR_INVALID_ARG, "output shape is not correct");
-#define UNSUP(msg) do { set_error("median3x3: %s", msg); return MI_ERR_UNSUPPORTED; } while (0)
+    const char *const who = "median3x3";
     if (in->dtype == MI_F64 && out->dtype == MI_F64)
         return run_median3x3_f64(in, out, filter_mode(mode[1]), filter_mode(mode[0]), cval, resolve_stream(stream));
     if (in->dtype == out->dtype && (in->dtype == MI_U16 || in->dtype == MI_I16))
         return run_median3x3_16(in, out, filter_mode(mode[1]), filter_mode(mode[0]), cval, resolve_stream(stream));
     if ((in->ndim != 2 && in->ndim != 3) || in->dtype != out->dtype || (in->dtype != MI_F32 && in->dtype != MI_U8))
-        UNSUP("needs 2-D / 3-D float32, float64, uint8, uint16 or int16 in/out");
-    if (!is_contiguous(in) || !is_contiguous(out)) UNSUP("needs C-contiguous arrays");
-    if (in->data == out->data) UNSUP("in-place");
+        MI_UNSUP(who, "needs 2-D / 3-D float32, float64, uint8, uint16 or int16 in/out");
+    if (!is_contiguous(in) || !is_contiguous(out)) MI_UNSUP(who, "needs C-contiguous arrays");
+    if (in->data == out->data) MI_UNSUP(who, "in-place");
     const int nd = in->ndim;
     const int64_t nz = nd == 3 ? in->shape[0] : 1, ny = in->shape[nd - 2], nx = in->shape[nd - 1];
     if (nz < 1 || ny < 1 || nx < 1) return MI_OK;
-    if (((uintptr_t)in->data & 15) || ((uintptr_t)out->data & 15)) UNSUP("needs 16-byte aligned data");
+    if (((uintptr_t)in->data & 15) || ((uintptr_t)out->data & 15)) MI_UNSUP(who, "needs 16-byte aligned data");
     const int my = filter_mode(mode[0]), mx = filter_mode(mode[1]);
     hipStream_t s = resolve_stream(stream);
     if (in->dtype == MI_U8) {
-        if (nx < 32 || (nx & 15) || (nx & 1023) == 16) UNSUP("x extent must be a multiple of 16, >= 32");
-        if (nz * ny * nx >= ((int64_t)1 << 31)) UNSUP("needs an array < 2 GiB");
+        if (nx < 32 || (nx & 15) || (nx & 1023) == 16) MI_UNSUP(who, "x extent must be a multiple of 16, >= 32");
+        if (nz * ny * nx >= ((int64_t)1 << 31)) MI_UNSUP(who, "needs an array < 2 GiB");
         if ((my == MI_MODE_CONSTANT || mx == MI_MODE_CONSTANT) && !(cval >= 0 && cval <= 255 && cval == (double)(int)cval))
-            UNSUP("cval is not a uint8 value");
+            MI_UNSUP(who, "cval is not a uint8 value");
         return run_median3x3_u8((const uint8_t *)in->data, (uint8_t *)out->data, (int)nz, (int)ny, (int)nx, mx, my, (int)cval, s);
     }
-    if (nx < 8 || (nx & 3)) UNSUP("x extent must be a multiple of 4, >= 8");
-    { const int64_t tail = nx & 255; if (tail != 0 && tail < 8) UNSUP("x extent unsuitable for the streaming x window"); }
-    if (nz * ny * nx * 4 >= ((int64_t)1 << 31)) UNSUP("needs an array < 2 GiB");
+    if (nx < 8 || (nx & 3)) MI_UNSUP(who, "x extent must be a multiple of 4, >= 8");
+    { const int64_t tail = nx & 255; if (tail != 0 && tail < 8) MI_UNSUP(who, "x extent unsuitable for the streaming x window"); }
+    if (nz * ny * nx * 4 >= ((int64_t)1 << 31)) MI_UNSUP(who, "needs an array < 2 GiB");
     Med2dParams p;
     memset(&p, 0, sizeof(p));
     p.nx = (int)nx; p.ny = (int)ny; p.nz = (int)nz;
@@ -192,5 +192,4 @@ extern "C" int mi_median3x3(const mi_array *in, const mi_array *out, const int m
     hipLaunchKernelGGL(median3x3_f32_kernel, dim3((waves + 3) / 4), dim3(256), 0, s, (const float *)in->data, (float *)out->data, p);
     MI_HIP(hipGetLastError());
     return MI_OK;
-#undef UNSUP
 }

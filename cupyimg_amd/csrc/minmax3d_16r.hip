@@ -10,6 +10,7 @@
 // either side for the seven-wide window.
 #include "nd_common.hpp"
 #include "sep_common.hpp"
+#include "stream3d.hpp"          // pack_cval2
 
 namespace mi {
 
@@ -198,7 +199,7 @@ int minmax3d_16_ragged(const mi_array *in, const mi_array *out, const int size[3
     memset(&p, 0, sizeof(p));
     p.nx = (int)nx; p.ny = (int)ny; p.nz = (int)nz;
     p.mz = filter_mode(mode[0]); p.my = filter_mode(mode[1]); p.mx = filter_mode(mode[2]);
-    p.cval2 = ((unsigned)cval & 0xffffu) * 0x10001u;
+    p.cval2 = pack_cval2(cval);
     p.L = (int)((nx + 7) / 8);
     p.rpw = 64 / p.L;
     p.nyb = (int)((ny + kS16rYB - 1) / kS16rYB);

@@ -452,20 +452,7 @@ template <int WA, bool IS_MAX>
 static int launch_runs_u8(const uint8_t *in, uint8_t *out, U8RunParams &p, hipStream_t s)
 {
     const int nlines = p.nz * p.nxt;
-    int nch = 1;
-    {
-        double best = 1e300;
-        for (int c = 1; c <= p.ny && c <= 2048; c++) {
-            const int chunk = (p.ny + c - 1) / c;
-            if (c > 1 && chunk < 8) break;
-            const int real = (p.ny + chunk - 1) / chunk;
-            const double rounds = std::max(1.0, (double)nlines * real / 4096.0);
-            const double cost = rounds * (chunk + (WA - 1) + 4.0);
-            if (cost < best * 0.999) { best = cost; nch = real; }
-        }
-    }
-    p.chunk = (p.ny + nch - 1) / nch;
-    p.nchunks = (p.ny + p.chunk - 1) / p.chunk;
+    plan_stream_chunks(nlines, p.ny, WA - 1, 8, 2048, &p.chunk, &p.nchunks);
     const int waves = nlines * p.nchunks;
     p.swz = xcd_swizzle_for((size_t)p.nx * p.ny * p.nz);
     hipLaunchKernelGGL((runs_minmax_u8_kernel<WA, IS_MAX>), dim3((waves + 3) / 4), dim3(256), 0, s, in, out, p);
@@ -819,20 +806,7 @@ static int launch_box2d_u8(const uint8_t *in, uint8_t *out, U8BoxParams &p, hipS
 {
     const int nlines = (p.axis == 0 ? p.ny : p.nz) * p.nxt;
     const int nA = p.axis == 0 ? p.nz : p.ny;
-    int nch = 1;
-    {
-        double best = 1e300;
-        for (int c = 1; c <= nA && c <= 2048; c++) {
-            const int chunk = (nA + c - 1) / c;
-            if (c > 1 && chunk < 8) break;
-            const int real = (nA + chunk - 1) / chunk;
-            const double rounds = std::max(1.0, (double)nlines * real / 4096.0);
-            const double cost = rounds * (chunk + (WY - 1) + 4.0);
-            if (cost < best * 0.999) { best = cost; nch = real; }
-        }
-    }
-    p.chunk = (nA + nch - 1) / nch;
-    p.nchunks = (nA + p.chunk - 1) / p.chunk;
+    plan_stream_chunks(nlines, nA, WY - 1, 8, 2048, &p.chunk, &p.nchunks);
     const int waves = nlines * p.nchunks;
     p.swz = xcd_swizzle_for((size_t)p.nx * p.ny * p.nz);
     hipLaunchKernelGGL((box2d_u8_kernel<WX, WY>), dim3((waves + 3) / 4), dim3(256), 0, s, in, out, p);
@@ -1006,10 +980,10 @@ int run_median3x3_u8(const uint8_t *in, uint8_t *out, int nz, int ny, int nx, in
     memset(&p, 0, sizeof(p));
     p.nx = nx; p.ny = ny; p.nz = nz;
     p.axis = 1; p.oa = 1; p.ma = my; p.mx = mx;
-    p.cval4 = (unsigned)cval * 0x01010101u;
+    p.cval4 = pack_cval4(cval);
     p.nxt = (nx + 1023) / 1024;
     const int nlines = nz * p.nxt;
-    int nch = (4096 + nlines - 1) / nlines;
+    int nch = (kStreamResidentWaves + nlines - 1) / nlines;      // fill the chip once, chunks of at least 8 rows
     if (nch > ny / 8) nch = ny / 8;
     if (nch < 1) nch = 1;
     p.chunk = (ny + nch - 1) / nch;
@@ -1027,22 +1001,7 @@ static int launch_u8(const uint8_t *in, uint8_t *out, U8StreamParams &p, hipStre
     const int nA = p.axis == 0 ? p.nz : p.ny;
     const int nother = p.axis == 0 ? p.ny : p.nz;
     const int nlines = nother * p.nxt;
-    // chunks along the streamed axis: time ~ rounds x (chunk + ramp) with 256 CUs x 16 resident waves; volumes have
-    // many lines and get long chunks, images (a handful of 1024-pixel columns) many short ones
-    int nch = 1;
-    {
-        double best = 1e300;
-        for (int c = 1; c <= nA && c <= 2048; c++) {
-            const int chunk = (nA + c - 1) / c;
-            if (c > 1 && chunk < 8) break;
-            const int real = (nA + chunk - 1) / chunk;
-            const double rounds = std::max(1.0, (double)nlines * real / 4096.0);
-            const double cost = rounds * (chunk + (WA - 1) + 4.0);
-            if (cost < best * 0.999) { best = cost; nch = real; }
-        }
-    }
-    p.chunk = (nA + nch - 1) / nch;
-    p.nchunks = (nA + p.chunk - 1) / p.chunk;
+    plan_stream_chunks(nlines, nA, WA - 1, 8, 2048, &p.chunk, &p.nchunks);
     const int waves = nlines * p.nchunks;
     p.swz = xcd_swizzle_for((size_t)p.nx * p.ny * p.nz);
     hipLaunchKernelGGL((stream_minmax_u8_kernel<WX, WA, IS_MAX>), dim3((waves + 3) / 4), dim3(256), 0, s, in, out, p);
@@ -1393,6 +1352,47 @@ static int launch_u8_fused_w(int w, const uint8_t *in, uint8_t *out, U8FusedPara
     }
 }
 
+// What the entry points below ask of their arrays, and where they differ.  The streaming kernels need nx >= 32 (the
+// last tile needs two lanes, hence also no tile of 16 voxels after full ones: the tail rule), the fused split kernel
+// nx >= 64.  The remaining differences are in which refusal comes first and how it is worded, nothing more.
+enum {
+    U8G_2D = 1,            // images are taken as one-plane volumes
+    U8G_BOOL = 2,          // bool arrays too (the same bytes)
+    U8G_NO_TAIL = 4,       // no x window: a last tile of one lane will do
+    U8G_SIZE_FIRST = 8,    // the 2 GiB test comes before the x extent test
+    U8G_VOLUME = 16,       // the 2 GiB refusal says "volume", not "array"
+    U8G_DISTINCT = 32,     // contiguity and in-place are one refusal
+};
+
+// geometry shared by the uint8 entry points (the counterpart of geometry16(), minmax_16.hip): the extents, or the refusal
+static int geometry_u8(const mi_array *in, const mi_array *out, const char *who, int min_nx, int flags, int64_t *nz, int64_t *ny, int64_t *nx)
+{
+    const bool images = flags & U8G_2D;
+    if (flags & U8G_BOOL) {
+        if (in->ndim != 3 || (in->dtype != MI_U8 && in->dtype != MI_BOOL) || out->dtype != in->dtype) MI_UNSUP(who, "needs 3-D uint8 / bool in/out");
+    } else if ((in->ndim != 3 && !(images && in->ndim == 2)) || in->dtype != MI_U8 || out->dtype != MI_U8) {
+        MI_UNSUP(who, images ? "needs 2-D / 3-D uint8 in/out" : "needs 3-D uint8 in/out");
+    }
+    if (flags & U8G_DISTINCT) {
+        if (!is_contiguous(in) || !is_contiguous(out) || in->data == out->data) MI_UNSUP(who, "needs distinct C-contiguous arrays");
+    } else {
+        if (!is_contiguous(in) || !is_contiguous(out)) MI_UNSUP(who, "needs C-contiguous arrays");
+        if (in->data == out->data) MI_UNSUP(who, "in-place");
+    }
+    const int nd = in->ndim;
+    *nz = nd == 3 ? in->shape[0] : 1; *ny = in->shape[nd - 2]; *nx = in->shape[nd - 1];
+    const bool too_large = *nz * *ny * *nx >= ((int64_t)1 << 31);
+    const char *const large_msg = (flags & U8G_VOLUME) ? "needs a volume < 2 GiB" : "needs an array < 2 GiB";
+    if ((flags & U8G_SIZE_FIRST) && too_large) MI_UNSUP(who, large_msg);
+    if (*nz < 1 || *ny < 1 || *nx < min_nx || (*nx & 15) || (!(flags & U8G_NO_TAIL) && (*nx & 1023) == 16)) {
+        set_error("%s: x extent must be a multiple of 16, >= %d", who, min_nx);
+        return MI_ERR_UNSUPPORTED;
+    }
+    if (too_large) MI_UNSUP(who, large_msg);
+    if (((uintptr_t)in->data & 15) || ((uintptr_t)out->data & 15)) MI_UNSUP(who, "needs 16-byte aligned data");
+    return MI_OK;
+}
+
 }  // namespace mi
 
 using namespace mi;
@@ -1412,17 +1412,13 @@ extern "C" int mi_minmax3d_u8_planes(const mi_array *in, const mi_array *out, co
     MI_REQUIRE(size && origin && mode && planes, MI_ERR_INVALID_ARG, "NULL argument");
     MI_REQUIRE(nranges >= 1 && nranges <= 2, MI_ERR_INVALID_ARG, "one or two plane ranges");
     MI_REQUIRE(same_shape(in, out), MI_ERR_INVALID_ARG, "output shape is not correct");
-#define UNSUP(msg) do { set_error("minmax3d_u8_planes: %s", msg); return MI_ERR_UNSUPPORTED; } while (0)
-    if (in->ndim != 3 || in->dtype != MI_U8 || out->dtype != MI_U8) UNSUP("needs 3-D uint8 in/out");
-    if (!is_contiguous(in) || !is_contiguous(out) || in->data == out->data) UNSUP("needs distinct C-contiguous arrays");
-    const int64_t nz = in->shape[0], ny = in->shape[1], nx = in->shape[2];
-    if (nz < 1 || ny < 1 || nx < 64 || (nx & 15) || (nx & 1023) == 16) UNSUP("x extent must be a multiple of 16, >= 64");
-    if (nz * ny * nx >= ((int64_t)1 << 31)) UNSUP("needs a volume < 2 GiB");
-    if (((uintptr_t)in->data & 15) || ((uintptr_t)out->data & 15)) UNSUP("needs 16-byte aligned data");
+    const char *const who = "minmax3d_u8_planes";
+    int64_t nz, ny, nx;
+    if ((rc = geometry_u8(in, out, who, 64, U8G_DISTINCT | U8G_VOLUME, &nz, &ny, &nx))) return rc;
     const int w = size[0];
-    if (size[1] != w || size[2] != w || (w != 3 && w != 5 && w != 7)) UNSUP("cubic sizes 3 / 5 / 7 only");
-    if (origin[0] || origin[1] || origin[2]) UNSUP("origin must be 0");
-    if (cval < 0 || cval > 255) UNSUP("cval outside uint8");
+    if (size[1] != w || size[2] != w || (w != 3 && w != 5 && w != 7)) MI_UNSUP(who, "cubic sizes 3 / 5 / 7 only");
+    if (origin[0] || origin[1] || origin[2]) MI_UNSUP(who, "origin must be 0");
+    if (!cval_fits_u8(cval)) MI_UNSUP(who, "cval outside uint8");
     int64_t prev_end = 0;
     for (int r = 0; r < nranges; r++) {
         const int64_t b = planes[2 * r], e = planes[2 * r + 1];
@@ -1437,7 +1433,7 @@ extern "C" int mi_minmax3d_u8_planes(const mi_array *in, const mi_array *out, co
         memset(&f, 0, sizeof(f));
         f.nx = (int)nx; f.ny = (int)ny; f.nz = (int)nz;
         f.mz = filter_mode(mode[0]); f.my = filter_mode(mode[1]); f.mx = filter_mode(mode[2]);
-        f.cval4 = (unsigned)cval * 0x01010101u;
+        f.cval4 = pack_cval4(cval);
         f.zb = (int)b; f.zn = (int)(e - b);
         const bool has_const = f.mz == MI_MODE_CONSTANT || f.my == MI_MODE_CONSTANT || f.mx == MI_MODE_CONSTANT;
         rc = is_max ? launch_u8_fused_w<true>(w, (const uint8_t *)in->data, (uint8_t *)out->data, f, has_const, s)
@@ -1445,7 +1441,6 @@ extern "C" int mi_minmax3d_u8_planes(const mi_array *in, const mi_array *out, co
         if (rc != MI_OK) return rc;
     }
     return MI_OK;
-#undef UNSUP
 }
 
 namespace mi {
@@ -1461,25 +1456,22 @@ extern "C" int mi_minmax3d_u8(const mi_array *in, const mi_array *out, const int
     if ((rc = check_array(in, "in")) || (rc = check_array(out, "out"))) return rc;
     MI_REQUIRE(size && origin && mode, MI_ERR_INVALID_ARG, "NULL argument");
     MI_REQUIRE(same_shape(in, out), MI_ERR_INVALID_ARG, "output shape is not correct");
-#define UNSUP(msg) do { set_error("minmax3d_u8: %s", msg); return MI_ERR_UNSUPPORTED; } while (0)
-    if (in->ndim != 3 || in->dtype != MI_U8 || out->dtype != MI_U8) UNSUP("needs 3-D uint8 in/out");
-    if (!is_contiguous(in) || !is_contiguous(out)) UNSUP("needs C-contiguous arrays");
-    if (in->data == out->data) UNSUP("in-place");
-    const int64_t nz = in->shape[0], ny = in->shape[1], nx = in->shape[2];
-    if (nz * ny * nx >= ((int64_t)1 << 31)) UNSUP("needs a volume < 2 GiB");
-    if (nz >= 1 && ny >= 1 && (nx & 15) && cval >= 0 && cval <= 255 && !origin[0] && !origin[1] && !origin[2]) {
-        // r6: rows that are not a multiple of 16 bytes as they lie (cubic 3 / 5 / 7, volumes the caches hold)
+    // rows that are not a multiple of 16 bytes as they lie (cubic 3 / 5 / 7, volumes the caches hold)
+    if (in->ndim == 3 && in->dtype == MI_U8 && out->dtype == MI_U8 && is_contiguous(in) && is_contiguous(out) && in->data != out->data &&
+        in->shape[0] >= 1 && in->shape[1] >= 1 && (in->shape[2] & 15) && in->shape[0] * in->shape[1] * in->shape[2] < ((int64_t)1 << 31) &&
+        cval_fits_u8(cval) && !origin[0] && !origin[1] && !origin[2]) {
         rc = minmax3d_u8_ragged(in, out, size, mode, cval, is_max, resolve_stream(stream));
         if (rc != MI_ERR_UNSUPPORTED) return rc;
     }
-    if (nz < 1 || ny < 1 || nx < 32 || (nx & 15) || (nx & 1023) == 16) UNSUP("x extent must be a multiple of 16, >= 32");
-    if (ny * nx >= ((int64_t)1 << 31)) UNSUP("plane too large");
-    if (((uintptr_t)in->data & 15) || ((uintptr_t)out->data & 15)) UNSUP("needs 16-byte aligned data");
+    const char *const who = "minmax3d_u8";
+    int64_t nz, ny, nx;
+    if ((rc = geometry_u8(in, out, who, 32, U8G_SIZE_FIRST | U8G_VOLUME, &nz, &ny, &nx))) return rc;
+    if (ny * nx >= ((int64_t)1 << 31)) MI_UNSUP(who, "plane too large");
     for (int a = 0; a < 3; a++) {
-        if (size[a] < 1 || !(size[a] & 1) || origin[a] != 0) UNSUP("sizes must be odd with origin 0");
+        if (size[a] < 1 || !(size[a] & 1) || origin[a] != 0) MI_UNSUP(who, "sizes must be odd with origin 0");
     }
-    if (size[2] > 9 || size[0] > 13 || size[1] > 13) UNSUP("size too large for the register kernels");
-    if (cval < 0 || cval > 255) UNSUP("cval outside uint8");
+    if (size[2] > 9 || size[0] > 13 || size[1] > 13) MI_UNSUP(who, "size too large for the register kernels");
+    if (!cval_fits_u8(cval)) MI_UNSUP(who, "cval outside uint8");
     hipStream_t s = resolve_stream(stream);
 
     U8StreamParams p;
@@ -1487,7 +1479,7 @@ extern "C" int mi_minmax3d_u8(const mi_array *in, const mi_array *out, const int
     p.nx = (int)nx; p.ny = (int)ny; p.nz = (int)nz;
     p.nxt = (int)((nx + 1023) / 1024);
     p.mx = filter_mode(mode[2]);
-    p.cval4 = (unsigned)cval * 0x01010101u;
+    p.cval4 = pack_cval4(cval);
     const uint8_t *ip = (const uint8_t *)in->data;
     uint8_t *op = (uint8_t *)out->data;
 
@@ -1531,7 +1523,6 @@ extern "C" int mi_minmax3d_u8(const mi_array *in, const mi_array *out, const int
     if (tmp) pool_free(tmp);
     if (rc == MI_ERR_UNSUPPORTED) set_error("minmax3d_u8: no kernel for this size");
     return rc;
-#undef UNSUP
 }
 
 /* Flat footprint given as centred runs per row (declared in include/mi355img.h). */
@@ -1542,30 +1533,24 @@ extern "C" int mi_minmax_runs_u8(const mi_array *in, const mi_array *out, int nr
     if ((rc = check_array(in, "in")) || (rc = check_array(out, "out"))) return rc;
     MI_REQUIRE(half_width && mode, MI_ERR_INVALID_ARG, "NULL argument");
     MI_REQUIRE(same_shape(in, out), MI_ERR_INVALID_ARG, "output shape is not correct");
-#define UNSUP(msg) do { set_error("minmax_runs_u8: %s", msg); return MI_ERR_UNSUPPORTED; } while (0)
-    if ((in->ndim != 2 && in->ndim != 3) || in->dtype != MI_U8 || out->dtype != MI_U8) UNSUP("needs 2-D / 3-D uint8 in/out");
-    if (!is_contiguous(in) || !is_contiguous(out)) UNSUP("needs C-contiguous arrays");
-    if (in->data == out->data) UNSUP("in-place");
-    const int nd = in->ndim;
-    const int64_t nz = nd == 3 ? in->shape[0] : 1, ny = in->shape[nd - 2], nx = in->shape[nd - 1];
-    if (nz < 1 || ny < 1 || nx < 32 || (nx & 15) || (nx & 1023) == 16) UNSUP("x extent must be a multiple of 16, >= 32");
-    if (nz * ny * nx >= ((int64_t)1 << 31)) UNSUP("needs an array < 2 GiB");
-    if (((uintptr_t)in->data & 15) || ((uintptr_t)out->data & 15)) UNSUP("needs 16-byte aligned data");
-    if (nrows < 1 || nrows > 9 || !(nrows & 1)) UNSUP("1, 3, 5, 7 or 9 footprint rows");
-    if (cval < 0 || cval > 255) UNSUP("cval outside uint8");
+    const char *const who = "minmax_runs_u8";
+    int64_t nz, ny, nx;
+    if ((rc = geometry_u8(in, out, who, 32, U8G_2D, &nz, &ny, &nx))) return rc;
+    if (nrows < 1 || nrows > 9 || !(nrows & 1)) MI_UNSUP(who, "1, 3, 5, 7 or 9 footprint rows");
+    if (!cval_fits_u8(cval)) MI_UNSUP(who, "cval outside uint8");
     U8RunParams p;
     memset(&p, 0, sizeof(p));
     bool any = false;
     for (int r = 0; r < 9; r++) p.hw[r] = -1;
     for (int r = 0; r < nrows; r++) {
-        if (half_width[r] < -1 || half_width[r] > 4) UNSUP("runs of at most 9 pixels");
+        if (half_width[r] < -1 || half_width[r] > 4) MI_UNSUP(who, "runs of at most 9 pixels");
         p.hw[r] = half_width[r];
         any = any || half_width[r] >= 0;
     }
-    if (!any) UNSUP("empty footprint");
+    if (!any) MI_UNSUP(who, "empty footprint");
     p.nx = (int)nx; p.ny = (int)ny; p.nz = (int)nz;
     p.my = filter_mode(mode[0]); p.mx = filter_mode(mode[1]);
-    p.cval4 = (unsigned)cval * 0x01010101u;
+    p.cval4 = pack_cval4(cval);
     p.nxt = (int)((nx + 1023) / 1024);
     hipStream_t s = resolve_stream(stream);
     const uint8_t *ip = (const uint8_t *)in->data;
@@ -1579,7 +1564,6 @@ extern "C" int mi_minmax_runs_u8(const mi_array *in, const mi_array *out, int nr
     default: RUNS(9);
     }
 #undef RUNS
-#undef UNSUP
 }
 
 /* 3 x 3 x 3 footprint of centred x runs on a uint8 / bool volume (declared in include/mi355img.h). */
@@ -1590,43 +1574,25 @@ extern "C" int mi_minmax_runs3d_u8(const mi_array *in, const mi_array *out, cons
     if ((rc = check_array(in, "in")) || (rc = check_array(out, "out"))) return rc;
     MI_REQUIRE(half_width && mode, MI_ERR_INVALID_ARG, "NULL argument");
     MI_REQUIRE(same_shape(in, out), MI_ERR_INVALID_ARG, "output shape is not correct");
-#define UNSUP(msg) do { set_error("minmax_runs3d_u8: %s", msg); return MI_ERR_UNSUPPORTED; } while (0)
-    if (in->ndim != 3 || (in->dtype != MI_U8 && in->dtype != MI_BOOL) || out->dtype != in->dtype) UNSUP("needs 3-D uint8 / bool in/out");
-    if (!is_contiguous(in) || !is_contiguous(out)) UNSUP("needs C-contiguous arrays");
-    if (in->data == out->data) UNSUP("in-place");
-    const int64_t nz = in->shape[0], ny = in->shape[1], nx = in->shape[2];
-    if (nz * ny * nx >= ((int64_t)1 << 31)) UNSUP("needs a volume < 2 GiB");
-    if (nz < 1 || ny < 1 || nx < 32 || (nx & 15) || (nx & 1023) == 16) UNSUP("x extent must be a multiple of 16, >= 32");
-    if (((uintptr_t)in->data & 15) || ((uintptr_t)out->data & 15)) UNSUP("needs 16-byte aligned data");
-    if (cval < 0 || cval > 255) UNSUP("cval outside uint8");
+    const char *const who = "minmax_runs3d_u8";
+    int64_t nz, ny, nx;
+    if ((rc = geometry_u8(in, out, who, 32, U8G_BOOL | U8G_SIZE_FIRST | U8G_VOLUME, &nz, &ny, &nx))) return rc;
+    if (!cval_fits_u8(cval)) MI_UNSUP(who, "cval outside uint8");
     U8Run3Params p;
     memset(&p, 0, sizeof(p));
     bool any = false;
     for (int k = 0; k < 9; k++) {
-        if (half_width[k] < -1 || half_width[k] > 1) UNSUP("runs of at most 3 voxels");
+        if (half_width[k] < -1 || half_width[k] > 1) MI_UNSUP(who, "runs of at most 3 voxels");
         p.hw[k / 3][k % 3] = half_width[k];
         any = any || half_width[k] >= 0;
     }
-    if (!any) UNSUP("empty footprint");
+    if (!any) MI_UNSUP(who, "empty footprint");
     p.nx = (int)nx; p.ny = (int)ny; p.nz = (int)nz;
     p.mz = filter_mode(mode[0]); p.my = filter_mode(mode[1]); p.mx = filter_mode(mode[2]);
-    p.cval4 = (unsigned)cval * 0x01010101u;
+    p.cval4 = pack_cval4(cval);
     p.nxt = (int)((nx + 1023) / 1024);
     const int nlines = p.ny * p.nxt;
-    int nch = 1;
-    {
-        double best = 1e300;
-        for (int c = 1; c <= p.nz && c <= 1024; c++) {
-            const int chunk = (p.nz + c - 1) / c;
-            if (c > 1 && chunk < 8) break;
-            const int real = (p.nz + chunk - 1) / chunk;
-            const double rounds = std::max(1.0, (double)nlines * real / 4096.0);
-            const double cost = rounds * (chunk + 2 + 4.0);
-            if (cost < best * 0.999) { best = cost; nch = real; }
-        }
-    }
-    p.chunk = (p.nz + nch - 1) / nch;
-    p.nchunks = (p.nz + p.chunk - 1) / p.chunk;
+    plan_stream_chunks(nlines, p.nz, 2, 8, 1024, &p.chunk, &p.nchunks);
     const int waves = nlines * p.nchunks;
     p.swz = xcd_swizzle_for((size_t)nx * ny * nz);
     hipStream_t s = resolve_stream(stream);
@@ -1636,7 +1602,6 @@ extern "C" int mi_minmax_runs3d_u8(const mi_array *in, const mi_array *out, cons
         hipLaunchKernelGGL(runs3d_minmax_u8_kernel<false>, dim3((waves + 3) / 4), dim3(256), 0, s, (const uint8_t *)in->data, (uint8_t *)out->data, p);
     MI_HIP(hipGetLastError());
     return MI_OK;
-#undef UNSUP
 }
 
 /* uniform_filter on a uint8 image / slice-wise on a uint8 volume, uint8 result (declared in include/mi355img.h). */
@@ -1647,28 +1612,22 @@ extern "C" int mi_uniform2d_u8(const mi_array *in, const mi_array *out, const in
     if ((rc = check_array(in, "in")) || (rc = check_array(out, "out"))) return rc;
     MI_REQUIRE(size && mode, MI_ERR_INVALID_ARG, "NULL argument");
     MI_REQUIRE(same_shape(in, out), MI_ERR_INVALID_ARG, "output shape is not correct");
-#define UNSUP(msg) do { set_error("uniform2d_u8: %s", msg); return MI_ERR_UNSUPPORTED; } while (0)
-    if ((in->ndim != 2 && in->ndim != 3) || in->dtype != MI_U8 || out->dtype != MI_U8) UNSUP("needs 2-D / 3-D uint8 in/out");
-    if (!is_contiguous(in) || !is_contiguous(out)) UNSUP("needs C-contiguous arrays");
-    if (in->data == out->data) UNSUP("in-place");
-    const int nd = in->ndim;
-    const int64_t nz = nd == 3 ? in->shape[0] : 1, ny = in->shape[nd - 2], nx = in->shape[nd - 1];
-    if (nz < 1 || ny < 1 || nx < 32 || (nx & 15) || (nx & 1023) == 16) UNSUP("x extent must be a multiple of 16, >= 32");
-    if (nz * ny * nx >= ((int64_t)1 << 31)) UNSUP("needs an array < 2 GiB");
-    if (((uintptr_t)in->data & 15) || ((uintptr_t)out->data & 15)) UNSUP("needs 16-byte aligned data");
+    const char *const who = "uniform2d_u8";
+    int64_t nz, ny, nx;
+    if ((rc = geometry_u8(in, out, who, 32, U8G_2D, &nz, &ny, &nx))) return rc;
     const int wy = size[0], wx = size[1];
-    if (wy < 1 || wy > 9 || !(wy & 1) || wx < 1 || wx > 9 || !(wx & 1)) UNSUP("sizes must be odd and <= 9");
-    if (wy == 1 && wx == 1) UNSUP("nothing to filter");
+    if (wy < 1 || wy > 9 || !(wy & 1) || wx < 1 || wx > 9 || !(wx & 1)) MI_UNSUP(who, "sizes must be odd and <= 9");
+    if (wy == 1 && wx == 1) MI_UNSUP(who, "nothing to filter");
     const int oy = wy / 2 + origin_y;
     if (oy < 0 || oy >= wy) { set_error("invalid origin"); return MI_ERR_INVALID_ARG; }
-    if (cval < 0 || cval > 255) UNSUP("cval outside uint8");
+    if (!cval_fits_u8(cval)) MI_UNSUP(who, "cval outside uint8");
     U8BoxParams p;
     memset(&p, 0, sizeof(p));
     p.nx = (int)nx; p.ny = (int)ny; p.nz = (int)nz;
     p.axis = 1;
     p.oy = oy;
     p.my = filter_mode(mode[0]); p.mx = filter_mode(mode[1]);
-    p.cval4 = (unsigned)cval * 0x01010101u;
+    p.cval4 = pack_cval4(cval);
     p.nxt = (int)((nx + 1023) / 1024);
     p.ry = (float)(1.0 / wy); p.rx = (float)(1.0 / wx);
     hipStream_t s = resolve_stream(stream);
@@ -1681,7 +1640,6 @@ extern "C" int mi_uniform2d_u8(const mi_array *in, const mi_array *out, const in
     case 7: return launch_box2d_u8_wy<7>(wy, ip, op, p, s);
     default: return launch_box2d_u8_wy<9>(wy, ip, op, p, s);
     }
-#undef UNSUP
 }
 
 /* The z pass of uniform_filter on a uint8 volume (uint8 intermediate, as SciPy stores it): trunc(sum of size_z planes /
@@ -1692,27 +1650,21 @@ extern "C" int mi_uniform_z_u8(const mi_array *in, const mi_array *out, int size
     int rc;
     if ((rc = check_array(in, "in")) || (rc = check_array(out, "out"))) return rc;
     MI_REQUIRE(same_shape(in, out), MI_ERR_INVALID_ARG, "output shape is not correct");
-#define UNSUP(msg) do { set_error("uniform_z_u8: %s", msg); return MI_ERR_UNSUPPORTED; } while (0)
-    if (in->ndim != 3 || in->dtype != MI_U8 || out->dtype != MI_U8) UNSUP("needs 3-D uint8 in/out");
-    if (!is_contiguous(in) || !is_contiguous(out)) UNSUP("needs C-contiguous arrays");
-    if (in->data == out->data) UNSUP("in-place");
-    const int64_t nz = in->shape[0], ny = in->shape[1], nx = in->shape[2];
-    if (nz < 1 || ny < 1 || nx < 32 || (nx & 15)) UNSUP("x extent must be a multiple of 16, >= 32");
-    if (nz * ny * nx >= ((int64_t)1 << 31)) UNSUP("needs an array < 2 GiB");
-    if (((uintptr_t)in->data & 15) || ((uintptr_t)out->data & 15)) UNSUP("needs 16-byte aligned data");
-    if (size_z < 3 || size_z > 9 || !(size_z & 1)) UNSUP("odd size 3 .. 9");
+    const char *const who = "uniform_z_u8";
+    int64_t nz, ny, nx;
+    if ((rc = geometry_u8(in, out, who, 32, U8G_NO_TAIL, &nz, &ny, &nx))) return rc;
+    if (size_z < 3 || size_z > 9 || !(size_z & 1)) MI_UNSUP(who, "odd size 3 .. 9");
     const int oz = size_z / 2 + origin_z;
     if (oz < 0 || oz >= size_z) { set_error("invalid origin"); return MI_ERR_INVALID_ARG; }
-    if (cval < 0 || cval > 255) UNSUP("cval outside uint8");
+    if (!cval_fits_u8(cval)) MI_UNSUP(who, "cval outside uint8");
     U8BoxParams p;
     memset(&p, 0, sizeof(p));
     p.nx = (int)nx; p.ny = (int)ny; p.nz = (int)nz;
     p.axis = 0;
     p.oy = oz;
     p.my = filter_mode(mode_z); p.mx = MI_MODE_REFLECT;
-    p.cval4 = (unsigned)cval * 0x01010101u;
+    p.cval4 = pack_cval4(cval);
     p.nxt = (int)((nx + 1023) / 1024);
     p.ry = (float)(1.0 / size_z); p.rx = 1.0f;
     return launch_box2d_u8_wy<1>(size_z, (const uint8_t *)in->data, (uint8_t *)out->data, p, resolve_stream(stream));
-#undef UNSUP
 }

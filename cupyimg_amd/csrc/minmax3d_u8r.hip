@@ -27,6 +27,7 @@
 // than the volume and the host takes this route only when hipMemGetAddressRange shows those bytes inside the allocation.
 #include "nd_common.hpp"
 #include "sep_common.hpp"
+#include "stream3d.hpp"          // pack_cval4
 
 namespace mi {
 
@@ -233,7 +234,7 @@ int minmax3d_u8_ragged(const mi_array *in, const mi_array *out, const int size[3
     memset(&p, 0, sizeof(p));
     p.nx = (int)nx; p.ny = (int)ny; p.nz = (int)nz;
     p.mz = filter_mode(mode[0]); p.my = filter_mode(mode[1]); p.mx = filter_mode(mode[2]);
-    p.cval4 = (unsigned)cval * 0x01010101u;
+    p.cval4 = pack_cval4(cval);
     p.L = (int)((nx + 15) / 16);
     p.rpw = 64 / p.L;
     p.nyb = (int)((ny + kU8rYB - 1) / kU8rYB);

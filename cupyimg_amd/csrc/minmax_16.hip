@@ -187,8 +187,6 @@ stream_minmax16_kernel(const uint16_t *__restrict__ in, uint16_t *__restrict__ o
     }
 }
 
-static void plan_chunks16(int nlines, int nA, int ramp, int *chunk, int *nchunks);
-
 // ---------------------------------------------------------------------------
 // Flat footprints whose rows are centred runs (disk, diamond, cross, square; see runs_minmax_u8_kernel in
 // minmax3d_u8.hip): the previous WA - 1 raw rows stay in registers as eight-dword windows, every footprint row
@@ -325,7 +323,7 @@ runs_minmax16_kernel(const uint16_t *__restrict__ in, uint16_t *__restrict__ out
 template <int WA>
 static int launch_runs16(const uint16_t *in, uint16_t *out, P16RunParams &p, bool is_max, bool is_signed, hipStream_t s)
 {
-    plan_chunks16(p.nz * p.nxt, p.ny, WA - 1, &p.chunk, &p.nchunks);
+    plan_stream_chunks(p.nz * p.nxt, p.ny, WA - 1, 8, 2048, &p.chunk, &p.nchunks);
     const int waves = p.nz * p.nxt * p.nchunks;
     p.swz = xcd_swizzle_for((size_t)p.nx * p.ny * p.nz * 2);
     const dim3 grid((waves + 3) / 4), block(256);
@@ -493,7 +491,7 @@ template <int WX, int WY>
 static int launch_box16(const uint16_t *in, uint16_t *out, Box16Params &p, bool is_signed, hipStream_t s)
 {
     const int nlines = (p.axis == 0 ? p.ny : p.nz) * p.nxt;
-    plan_chunks16(nlines, p.axis == 0 ? p.nz : p.ny, WY - 1, &p.chunk, &p.nchunks);
+    plan_stream_chunks(nlines, p.axis == 0 ? p.nz : p.ny, WY - 1, 8, 2048, &p.chunk, &p.nchunks);
     const int waves = nlines * p.nchunks;
     p.swz = xcd_swizzle_for((size_t)p.nx * p.ny * p.nz * 2);
     if (is_signed) hipLaunchKernelGGL((box2d_16_kernel<WX, WY, true>), dim3((waves + 3) / 4), dim3(256), 0, s, in, out, p);
@@ -633,28 +631,12 @@ median3x3_16_kernel(const uint16_t *__restrict__ in, uint16_t *__restrict__ out,
     }
 }
 
-static void plan_chunks16(int nlines, int nA, int ramp, int *chunk, int *nchunks)
-{
-    int nch = 1;
-    double best = 1e300;
-    for (int c = 1; c <= nA && c <= 2048; c++) {
-        const int ck = (nA + c - 1) / c;
-        if (c > 1 && ck < 8) break;
-        const int real = (nA + ck - 1) / ck;
-        const double rounds = std::max(1.0, (double)nlines * real / 4096.0);
-        const double cost = rounds * (ck + ramp + 4.0);
-        if (cost < best * 0.999) { best = cost; nch = real; }
-    }
-    *chunk = (nA + nch - 1) / nch;
-    *nchunks = (nA + *chunk - 1) / *chunk;
-}
-
 template <int WX, int WA, bool IS_MAX, bool SIGNED>
 static int launch16(const uint16_t *in, uint16_t *out, P16Params &p, hipStream_t s)
 {
     const int nA = p.axis == 0 ? p.nz : p.ny;
     const int nlines = (p.axis == 0 ? p.ny : p.nz) * p.nxt;
-    plan_chunks16(nlines, nA, WA - 1, &p.chunk, &p.nchunks);
+    plan_stream_chunks(nlines, nA, WA - 1, 8, 2048, &p.chunk, &p.nchunks);
     const int waves = nlines * p.nchunks;
     p.swz = xcd_swizzle_for((size_t)p.nx * p.ny * p.nz * 2);
     hipLaunchKernelGGL((stream_minmax16_kernel<WX, WA, IS_MAX, SIGNED>), dim3((waves + 3) / 4), dim3(256), 0, s, in, out, p);
@@ -687,19 +669,17 @@ static int pass16_any(bool is_max, bool is_signed, const uint16_t *in, uint16_t 
 // geometry shared by the two entry points below; 2-D arrays are one-plane volumes
 static int geometry16(const mi_array *in, const mi_array *out, const char *who, int64_t *nz, int64_t *ny, int64_t *nx)
 {
-#define UNSUP(msg) do { set_error("%s: %s", who, msg); return MI_ERR_UNSUPPORTED; } while (0)
     if ((in->ndim != 2 && in->ndim != 3) || in->dtype != out->dtype || (in->dtype != MI_U16 && in->dtype != MI_I16))
-        UNSUP("needs 2-D / 3-D uint16 or int16 in/out");
-    if (!is_contiguous(in) || !is_contiguous(out)) UNSUP("needs C-contiguous arrays");
-    if (in->data == out->data) UNSUP("in-place");
+        MI_UNSUP(who, "needs 2-D / 3-D uint16 or int16 in/out");
+    if (!is_contiguous(in) || !is_contiguous(out)) MI_UNSUP(who, "needs C-contiguous arrays");
+    if (in->data == out->data) MI_UNSUP(who, "in-place");
     const int nd = in->ndim;
     *nz = nd == 3 ? in->shape[0] : 1; *ny = in->shape[nd - 2]; *nx = in->shape[nd - 1];
-    if (*nz < 1 || *ny < 1 || *nx < 16 || (*nx & 7)) UNSUP("x extent must be a multiple of 8, >= 16");
+    if (*nz < 1 || *ny < 1 || *nx < 16 || (*nx & 7)) MI_UNSUP(who, "x extent must be a multiple of 8, >= 16");
     // the last tile needs two lanes: lane 0 takes the block left of the tile, lane `last` the block right of it
-    { const int64_t tail = *nx & 511; if (tail != 0 && tail < 16) UNSUP("x extent unsuitable for the streaming x window"); }
-    if (*nz * *ny * *nx * 2 >= ((int64_t)1 << 31)) UNSUP("needs an array < 2 GiB");
-    if (((uintptr_t)in->data & 15) || ((uintptr_t)out->data & 15)) UNSUP("needs 16-byte aligned data");
-#undef UNSUP
+    { const int64_t tail = *nx & 511; if (tail != 0 && tail < 16) MI_UNSUP(who, "x extent unsuitable for the streaming x window"); }
+    if (*nz * *ny * *nx * 2 >= ((int64_t)1 << 31)) MI_UNSUP(who, "needs an array < 2 GiB");
+    if (((uintptr_t)in->data & 15) || ((uintptr_t)out->data & 15)) MI_UNSUP(who, "needs 16-byte aligned data");
     return MI_OK;
 }
 
@@ -717,9 +697,9 @@ int run_median3x3_16(const mi_array *in, const mi_array *out, int mx, int my, do
     memset(&p, 0, sizeof(p));
     p.nx = (int)nx; p.ny = (int)ny; p.nz = (int)nz;
     p.axis = 1; p.oa = 1; p.ma = my; p.mx = mx;
-    p.cval2 = ((unsigned)(int)cval & 0xFFFFu) * 0x10001u;
+    p.cval2 = pack_cval2((int)cval);
     p.nxt = (int)((nx + 511) / 512);
-    plan_chunks16(p.nz * p.nxt, p.ny, 2, &p.chunk, &p.nchunks);
+    plan_stream_chunks(p.nz * p.nxt, p.ny, 2, 8, 2048, &p.chunk, &p.nchunks);
     const int waves = p.nz * p.nxt * p.nchunks;
     p.swz = xcd_swizzle_for((size_t)p.nx * p.ny * p.nz * 2);
     if (is_signed)
@@ -750,17 +730,17 @@ extern "C" int mi_minmax3d_16(const mi_array *in, const mi_array *out, const int
     // r6: rows that are not a multiple of 16 bytes as they lie (cubic 3 / 5 / 7, volumes the caches hold)
     if (in->ndim == 3 && in->dtype == out->dtype && (in->dtype == MI_U16 || in->dtype == MI_I16) && is_contiguous(in) && is_contiguous(out) &&
         in->data != out->data && (in->shape[2] & 7) && !origin[0] && !origin[1] && !origin[2] &&
-        cval >= (in->dtype == MI_I16 ? -32768 : 0) && cval <= (in->dtype == MI_I16 ? 32767 : 65535)) {
+        cval_fits_16(cval, in->dtype == MI_I16)) {
         rc = minmax3d_16_ragged(in, out, size, mode, cval, is_max, resolve_stream(stream));
         if (rc != MI_ERR_UNSUPPORTED) return rc;
     }
+    const char *const who = "minmax3d_16";
     int64_t nz, ny, nx;
-    if ((rc = geometry16(in, out, "minmax3d_16", &nz, &ny, &nx))) return rc;
-#define UNSUP(msg) do { set_error("minmax3d_16: %s", msg); return MI_ERR_UNSUPPORTED; } while (0)
+    if ((rc = geometry16(in, out, who, &nz, &ny, &nx))) return rc;
     for (int a = 0; a < 3; a++)
-        if (size[a] < 1 || size[a] > 9 || !(size[a] & 1) || origin[a] != 0) UNSUP("sizes must be odd, <= 9, with origin 0");
+        if (size[a] < 1 || size[a] > 9 || !(size[a] & 1) || origin[a] != 0) MI_UNSUP(who, "sizes must be odd, <= 9, with origin 0");
     const bool is_signed = in->dtype == MI_I16;
-    if (cval < (is_signed ? -32768 : 0) || cval > (is_signed ? 32767 : 65535)) UNSUP("cval outside the dtype");
+    if (!cval_fits_16(cval, is_signed)) MI_UNSUP(who, "cval outside the dtype");
     const int mz = filter_mode(mode[0]), my = filter_mode(mode[1]), mx = filter_mode(mode[2]);
     hipStream_t s = resolve_stream(stream);
     struct Pass { int axis, wa, oa, ma, wx; };
@@ -772,7 +752,7 @@ extern "C" int mi_minmax3d_16(const mi_array *in, const mi_array *out, const int
     if (w[2] > 1 && !fuse_xz && !fuse_xy) passes[np++] = {1, 1, 0, my, w[2]};
     if (w[0] > 1) passes[np++] = {0, w[0], w[0] / 2, mz, fuse_xz ? w[2] : 1};
     if (w[1] > 1) passes[np++] = {1, w[1], w[1] / 2, my, fuse_xy ? w[2] : 1};
-    if (np == 0) UNSUP("nothing to filter");
+    if (np == 0) MI_UNSUP(who, "nothing to filter");
     const size_t bytes = (size_t)(nz * ny * nx) * 2;
     void *tmp[2] = {nullptr, nullptr};
     for (int t = 0; t < np - 1 && t < 2; t++)
@@ -785,14 +765,13 @@ extern "C" int mi_minmax3d_16(const mi_array *in, const mi_array *out, const int
         memset(&p, 0, sizeof(p));
         p.nx = (int)nx; p.ny = (int)ny; p.nz = (int)nz;
         p.axis = q.axis; p.oa = q.oa; p.ma = q.ma; p.mx = mx;
-        p.cval2 = ((unsigned)cval & 0xFFFFu) * 0x10001u;
+        p.cval2 = pack_cval2(cval);
         p.nxt = (int)((nx + 511) / 512);
         rc = pass16_any(is_max != 0, is_signed, src, dst, p, q.wx, q.wa, s);
         src = dst;
     }
     for (int t = 0; t < 2; t++) if (tmp[t]) pool_free(tmp[t]);
     return rc;
-#undef UNSUP
 }
 
 /* Flat footprint given as centred runs per row, uint16 / int16 (declared in include/mi355img.h). */
@@ -803,25 +782,25 @@ extern "C" int mi_minmax_runs_16(const mi_array *in, const mi_array *out, int nr
     if ((rc = check_array(in, "in")) || (rc = check_array(out, "out"))) return rc;
     MI_REQUIRE(half_width && mode, MI_ERR_INVALID_ARG, "NULL argument");
     MI_REQUIRE(same_shape(in, out), MI_ERR_INVALID_ARG, "output shape is not correct");
+    const char *const who = "minmax_runs_16";
     int64_t nz, ny, nx;
-    if ((rc = geometry16(in, out, "minmax_runs_16", &nz, &ny, &nx))) return rc;
-#define UNSUP(msg) do { set_error("minmax_runs_16: %s", msg); return MI_ERR_UNSUPPORTED; } while (0)
-    if (nrows < 1 || nrows > 9 || !(nrows & 1)) UNSUP("1, 3, 5, 7 or 9 footprint rows");
+    if ((rc = geometry16(in, out, who, &nz, &ny, &nx))) return rc;
+    if (nrows < 1 || nrows > 9 || !(nrows & 1)) MI_UNSUP(who, "1, 3, 5, 7 or 9 footprint rows");
     const bool is_signed = in->dtype == MI_I16;
-    if (cval < (is_signed ? -32768 : 0) || cval > (is_signed ? 32767 : 65535)) UNSUP("cval outside the dtype");
+    if (!cval_fits_16(cval, is_signed)) MI_UNSUP(who, "cval outside the dtype");
     P16RunParams p;
     memset(&p, 0, sizeof(p));
     bool any = false;
     for (int r = 0; r < 9; r++) p.hw[r] = -1;
     for (int r = 0; r < nrows; r++) {
-        if (half_width[r] < -1 || half_width[r] > 4) UNSUP("runs of at most 9 pixels");
+        if (half_width[r] < -1 || half_width[r] > 4) MI_UNSUP(who, "runs of at most 9 pixels");
         p.hw[r] = half_width[r];
         any = any || half_width[r] >= 0;
     }
-    if (!any) UNSUP("empty footprint");
+    if (!any) MI_UNSUP(who, "empty footprint");
     p.nx = (int)nx; p.ny = (int)ny; p.nz = (int)nz;
     p.my = filter_mode(mode[0]); p.mx = filter_mode(mode[1]);
-    p.cval2 = ((unsigned)cval & 0xFFFFu) * 0x10001u;
+    p.cval2 = pack_cval2(cval);
     p.nxt = (int)((nx + 511) / 512);
     hipStream_t s = resolve_stream(stream);
     const uint16_t *ip = (const uint16_t *)in->data;
@@ -833,7 +812,6 @@ extern "C" int mi_minmax_runs_16(const mi_array *in, const mi_array *out, int nr
     case 7: return launch_runs16<7>(ip, op, p, is_max != 0, is_signed, s);
     default: return launch_runs16<9>(ip, op, p, is_max != 0, is_signed, s);
     }
-#undef UNSUP
 }
 
 /* uniform_filter on a uint16 / int16 image (volume: slice by slice), result in the same dtype (declared in
@@ -845,23 +823,23 @@ extern "C" int mi_uniform2d_16(const mi_array *in, const mi_array *out, const in
     if ((rc = check_array(in, "in")) || (rc = check_array(out, "out"))) return rc;
     MI_REQUIRE(size && mode, MI_ERR_INVALID_ARG, "NULL argument");
     MI_REQUIRE(same_shape(in, out), MI_ERR_INVALID_ARG, "output shape is not correct");
+    const char *const who = "uniform2d_16";
     int64_t nz, ny, nx;
-    if ((rc = geometry16(in, out, "uniform2d_16", &nz, &ny, &nx))) return rc;
-#define UNSUP(msg) do { set_error("uniform2d_16: %s", msg); return MI_ERR_UNSUPPORTED; } while (0)
+    if ((rc = geometry16(in, out, who, &nz, &ny, &nx))) return rc;
     const int wy = size[0], wx = size[1];
-    if (wy < 1 || wy > 9 || !(wy & 1) || wx < 1 || wx > 9 || !(wx & 1)) UNSUP("sizes must be odd and <= 9");
-    if (wy == 1 && wx == 1) UNSUP("nothing to filter");
+    if (wy < 1 || wy > 9 || !(wy & 1) || wx < 1 || wx > 9 || !(wx & 1)) MI_UNSUP(who, "sizes must be odd and <= 9");
+    if (wy == 1 && wx == 1) MI_UNSUP(who, "nothing to filter");
     const int oy = wy / 2 + origin_y;
     if (oy < 0 || oy >= wy) { set_error("invalid origin"); return MI_ERR_INVALID_ARG; }
     const bool is_signed = in->dtype == MI_I16;
-    if (cval < (is_signed ? -32768 : 0) || cval > (is_signed ? 32767 : 65535)) UNSUP("cval outside the dtype");
+    if (!cval_fits_16(cval, is_signed)) MI_UNSUP(who, "cval outside the dtype");
     Box16Params p;
     memset(&p, 0, sizeof(p));
     p.nx = (int)nx; p.ny = (int)ny; p.nz = (int)nz;
     p.axis = 1;
     p.oy = oy;
     p.my = filter_mode(mode[0]); p.mx = filter_mode(mode[1]);
-    p.cval2 = ((unsigned)cval & 0xFFFFu) * 0x10001u;
+    p.cval2 = pack_cval2(cval);
     p.nxt = (int)((nx + 511) / 512);
     p.ry = (float)(1.0 / wy); p.rx = (float)(1.0 / wx);
     hipStream_t s = resolve_stream(stream);
@@ -875,7 +853,6 @@ extern "C" int mi_uniform2d_16(const mi_array *in, const mi_array *out, const in
     case 7: return launch_box16_wy<7>(wy, ip, op, p, is_signed, s);
     default: return launch_box16_wy<9>(wy, ip, op, p, is_signed, s);
     }
-#undef UNSUP
 }
 
 /* The z pass of uniform_filter on a uint16 / int16 volume (declared in include/mi355img.h). */
@@ -885,25 +862,24 @@ extern "C" int mi_uniform_z_16(const mi_array *in, const mi_array *out, int size
     int rc;
     if ((rc = check_array(in, "in")) || (rc = check_array(out, "out"))) return rc;
     MI_REQUIRE(same_shape(in, out), MI_ERR_INVALID_ARG, "output shape is not correct");
+    const char *const who = "uniform_z_16";
     int64_t nz, ny, nx;
-    if ((rc = geometry16(in, out, "uniform_z_16", &nz, &ny, &nx))) return rc;
-#define UNSUP(msg) do { set_error("uniform_z_16: %s", msg); return MI_ERR_UNSUPPORTED; } while (0)
-    if (in->ndim != 3) UNSUP("needs a volume");
-    if (size_z < 3 || size_z > 9 || !(size_z & 1)) UNSUP("odd size 3 .. 9");
+    if ((rc = geometry16(in, out, who, &nz, &ny, &nx))) return rc;
+    if (in->ndim != 3) MI_UNSUP(who, "needs a volume");
+    if (size_z < 3 || size_z > 9 || !(size_z & 1)) MI_UNSUP(who, "odd size 3 .. 9");
     const int oz = size_z / 2 + origin_z;
     if (oz < 0 || oz >= size_z) { set_error("invalid origin"); return MI_ERR_INVALID_ARG; }
     const bool is_signed = in->dtype == MI_I16;
-    if (cval < (is_signed ? -32768 : 0) || cval > (is_signed ? 32767 : 65535)) UNSUP("cval outside the dtype");
+    if (!cval_fits_16(cval, is_signed)) MI_UNSUP(who, "cval outside the dtype");
     Box16Params p;
     memset(&p, 0, sizeof(p));
     p.nx = (int)nx; p.ny = (int)ny; p.nz = (int)nz;
     p.axis = 0;
     p.oy = oz;
     p.my = filter_mode(mode_z); p.mx = MI_MODE_REFLECT;
-    p.cval2 = ((unsigned)cval & 0xFFFFu) * 0x10001u;
+    p.cval2 = pack_cval2(cval);
     p.nxt = (int)((nx + 511) / 512);
     p.ry = (float)(1.0 / size_z); p.rx = 1.0f;
     note_kernel("mi::box2d_16_kernel<1,%d,%s> (uniform_filter in integer arithmetic: z window)", size_z, is_signed ? "int16" : "uint16");
     return launch_box16_wy<1>(size_z, (const uint16_t *)in->data, (uint16_t *)out->data, p, is_signed, resolve_stream(stream));
-#undef UNSUP
 }

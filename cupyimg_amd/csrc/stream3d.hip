@@ -337,20 +337,7 @@ template <int WA>
 static int launch_runs_f32(const float *in, float *out, RunsF32Params &p, bool is_max, hipStream_t s)
 {
     const int nlines = p.nz * p.nxt;
-    int nch = 1;
-    {
-        double best = 1e300;
-        for (int c = 1; c <= p.ny && c <= 1024; c++) {
-            const int chunk = (p.ny + c - 1) / c;
-            if (c > 1 && chunk < 16) break;
-            const int real = (p.ny + chunk - 1) / chunk;
-            const double rounds = std::max(1.0, (double)nlines * real / 4096.0);
-            const double cost = rounds * (chunk + (WA - 1) + 4.0);
-            if (cost < best * 0.999) { best = cost; nch = real; }
-        }
-    }
-    p.chunk = (p.ny + nch - 1) / nch;
-    p.nchunks = (p.ny + p.chunk - 1) / p.chunk;
+    plan_stream_chunks(nlines, p.ny, WA - 1, 16, 1024, &p.chunk, &p.nchunks);
     const int waves = nlines * p.nchunks;
     p.swz = xcd_swizzle_for((size_t)p.nx * p.ny * p.nz * 4);
     if (is_max) hipLaunchKernelGGL((runs_minmax_f32_kernel<WA, SP_MAX>), dim3((waves + 3) / 4), dim3(256), 0, s, in, out, p);
@@ -367,22 +354,7 @@ static int launch_stream(const float *in, float *out, StreamParams &p, hipStream
     const int nA = p.axis == 0 ? p.nz : p.ny;
     const int nother = p.axis == 0 ? p.ny : p.nz;
     const int nlines = nother * p.nxt;
-    // chunks along the streamed axis: time ~ rounds x (chunk + ramp), with 256 CUs x 16 resident waves;
-    // many lines (3-D volumes) -> few long chunks, few lines (2-D images, thin slabs) -> many short ones
-    int nch = 1;
-    {
-        double best = 1e300;
-        for (int c = 1; c <= nA && c <= 1024; c++) {
-            const int chunk = (nA + c - 1) / c;
-            if (c > 1 && chunk < 16) break;
-            const int real = (nA + chunk - 1) / chunk;
-            const double rounds = std::max(1.0, (double)nlines * real / 4096.0);
-            const double cost = rounds * (chunk + (WA - 1) + 4.0);
-            if (cost < best * 0.999) { best = cost; nch = real; }
-        }
-    }
-    p.chunk = (nA + nch - 1) / nch;
-    p.nchunks = (nA + p.chunk - 1) / p.chunk;
+    plan_stream_chunks(nlines, nA, WA - 1, 16, 1024, &p.chunk, &p.nchunks);
     const int waves = nlines * p.nchunks;
     constexpr int wpb = 4;                    // waves per workgroup; the whole pass is one launch (wid_base = 0)
     p.wpb = wpb;
@@ -393,9 +365,6 @@ static int launch_stream(const float *in, float *out, StreamParams &p, hipStream
     MI_HIP(hipGetLastError());
     return MI_OK;
 }
-
-// switch over odd tap counts 1..33 for one template slot
-#define MI_ODD_CASES(X) X(1) X(3) X(5) X(7) X(9) X(11) X(13) X(15) X(17) X(19) X(21) X(23) X(25) X(27) X(29) X(31) X(33)
 
 template <int WX>
 static int launch_stream_wa(int wa, const float *in, float *out, StreamParams &p, hipStream_t s)
@@ -505,6 +474,15 @@ extern "C" int mi_debug_stream_pass(const float *in, float *out, int nz, int ny,
     return run_stream_pass(in, out, nz, ny, nx, axis, wav, wa, oa, ma, wxv, wx, mx, cval, resolve_stream(stream));
 }
 
+// test hook: the chunk plan of a streaming launch (plan_stream_chunks, stream3d.hpp); host arithmetic only
+extern "C" int mi_debug_plan_stream_chunks(int nlines, int n_axis, int ramp, int min_chunk, int max_chunks, int *chunk, int *nchunks)
+{
+    MI_REQUIRE(chunk && nchunks, MI_ERR_INVALID_ARG, "NULL argument");
+    MI_REQUIRE(nlines >= 1 && n_axis >= 1 && ramp >= 0 && min_chunk >= 1 && max_chunks >= 1, MI_ERR_INVALID_ARG, "counts must be positive");
+    plan_stream_chunks(nlines, n_axis, ramp, min_chunk, max_chunks, chunk, nchunks);
+    return MI_OK;
+}
+
 /* Separable flat min / max filter on a float32 volume as streaming passes
  * (declared in include/mi355img.h). */
 extern "C" int mi_minmax3d_f32(const mi_array *in, const mi_array *out, const int size[3], const int origin[3],
@@ -514,10 +492,10 @@ extern "C" int mi_minmax3d_f32(const mi_array *in, const mi_array *out, const in
     if ((rc = check_array(in, "in")) || (rc = check_array(out, "out"))) return rc;
     MI_REQUIRE(size && origin && mode, MI_ERR_INVALID_ARG, "NULL argument");
     MI_REQUIRE(same_shape(in, out), MI_ERR_INVALID_ARG, "output shape is not correct");
-#define UNSUP(msg) do { set_error("minmax3d_f32: %s", msg); return MI_ERR_UNSUPPORTED; } while (0)
-    if (in->ndim != 3 || in->dtype != MI_F32 || out->dtype != MI_F32) UNSUP("needs 3-D float32 in/out");
-    if (!is_contiguous(in) || !is_contiguous(out)) UNSUP("needs C-contiguous arrays");
-    if (in->data == out->data) UNSUP("in-place");
+    const char *const who = "minmax3d_f32";
+    if (in->ndim != 3 || in->dtype != MI_F32 || out->dtype != MI_F32) MI_UNSUP(who, "needs 3-D float32 in/out");
+    if (!is_contiguous(in) || !is_contiguous(out)) MI_UNSUP(who, "needs C-contiguous arrays");
+    if (in->data == out->data) MI_UNSUP(who, "in-place");
     const int64_t nz = in->shape[0], ny = in->shape[1], nx = in->shape[2];
     if ((nx & 3) && nz >= 1 && ny >= 1) {
         // r6: rows that are not a multiple of four floats -- cubic sizes without origins in ONE launch on the rows as they
@@ -529,23 +507,23 @@ extern "C" int mi_minmax3d_f32(const mi_array *in, const mi_array *out, const in
             return run_minmax3d_f32_fused((const float *)in->data, (float *)out->data, (int)nz, (int)ny, (int)nx, 9, 4, 4,
                                           filter_mode(mode[2]), filter_mode(mode[1]), filter_mode(mode[0]), is_max != 0, resolve_stream(stream));
         }
-        UNSUP("rows that are not a multiple of 4 floats: cubic sizes 3 / 5 / 7 / 9 without origins only");
+        MI_UNSUP(who, "rows that are not a multiple of 4 floats: cubic sizes 3 / 5 / 7 / 9 without origins only");
     }
-    if (nz < 1 || ny < 1 || nx < 8 || (nx & 3)) UNSUP("x extent must be a multiple of 4, >= 8");
-    if (nz * ny * nx * 4 >= ((int64_t)1 << 31)) UNSUP("needs a volume < 2 GiB");
-    if (((uintptr_t)in->data & 15) || ((uintptr_t)out->data & 15)) UNSUP("needs 16-byte aligned data");
+    if (nz < 1 || ny < 1 || nx < 8 || (nx & 3)) MI_UNSUP(who, "x extent must be a multiple of 4, >= 8");
+    if (nz * ny * nx * 4 >= ((int64_t)1 << 31)) MI_UNSUP(who, "needs a volume < 2 GiB");
+    if (((uintptr_t)in->data & 15) || ((uintptr_t)out->data & 15)) MI_UNSUP(who, "needs 16-byte aligned data");
     int w[3], off[3];
     for (int a = 0; a < 3; a++) {
         w[a] = size[a];
-        if (w[a] < 1 || w[a] > 9 || !(w[a] & 1)) UNSUP("sizes must be odd and <= 9");
+        if (w[a] < 1 || w[a] > 9 || !(w[a] & 1)) MI_UNSUP(who, "sizes must be odd and <= 9");
         off[a] = w[a] / 2 + origin[a];
         if (off[a] < 0 || off[a] >= w[a]) { set_error("invalid origin"); return MI_ERR_INVALID_ARG; }
     }
-    if (origin[2] != 0) UNSUP("x origin must be 0");
+    if (origin[2] != 0) MI_UNSUP(who, "x origin must be 0");
     {
         const int nb = (w[2] / 2 + 3) / 4;
         const int64_t tail = nx & 255;
-        if (w[2] > 1 && (nx < 4 * nb + 4 || (tail != 0 && tail < 4 * nb + 4))) UNSUP("x extent unsuitable for the streaming x pass");
+        if (w[2] > 1 && (nx < 4 * nb + 4 || (tail != 0 && tail < 4 * nb + 4))) MI_UNSUP(who, "x extent unsuitable for the streaming x pass");
     }
     const int mz = filter_mode(mode[0]), my = filter_mode(mode[1]), mx = filter_mode(mode[2]);
     hipStream_t s = resolve_stream(stream);
@@ -563,7 +541,7 @@ extern "C" int mi_minmax3d_f32(const mi_array *in, const mi_array *out, const in
     if (w[2] > 1 && !fuse_xz && !fuse_xy) passes[np++] = {1, 1, 0, my, w[2]};      // x only (streams over y)
     if (w[0] > 1) passes[np++] = {0, w[0], off[0], mz, fuse_xz ? w[2] : 1};
     if (w[1] > 1) passes[np++] = {1, w[1], off[1], my, fuse_xy ? w[2] : 1};
-    if (np == 0) UNSUP("nothing to filter");
+    if (np == 0) MI_UNSUP(who, "nothing to filter");
     const size_t bytes = (size_t)(nz * ny * nx) * sizeof(float);
     void *tmp[2] = {nullptr, nullptr};
     for (int t = 0; t < np - 1 && t < 2; t++)
@@ -578,7 +556,6 @@ extern "C" int mi_minmax3d_f32(const mi_array *in, const mi_array *out, const in
     }
     for (int t = 0; t < 2; t++) if (tmp[t]) pool_free(tmp[t]);   // reuse is stream ordered
     return rc;
-#undef UNSUP
 }
 
 /* Flat footprint given as centred runs per row, float32 images (declared in include/mi355img.h). */
@@ -589,27 +566,27 @@ extern "C" int mi_minmax_runs_f32(const mi_array *in, const mi_array *out, int n
     if ((rc = check_array(in, "in")) || (rc = check_array(out, "out"))) return rc;
     MI_REQUIRE(half_width && mode, MI_ERR_INVALID_ARG, "NULL argument");
     MI_REQUIRE(same_shape(in, out), MI_ERR_INVALID_ARG, "output shape is not correct");
-#define UNSUP(msg) do { set_error("minmax_runs_f32: %s", msg); return MI_ERR_UNSUPPORTED; } while (0)
-    if ((in->ndim != 2 && in->ndim != 3) || in->dtype != MI_F32 || out->dtype != MI_F32) UNSUP("needs 2-D / 3-D float32 in/out");
-    if (!is_contiguous(in) || !is_contiguous(out)) UNSUP("needs C-contiguous arrays");
-    if (in->data == out->data) UNSUP("in-place");
+    const char *const who = "minmax_runs_f32";
+    if ((in->ndim != 2 && in->ndim != 3) || in->dtype != MI_F32 || out->dtype != MI_F32) MI_UNSUP(who, "needs 2-D / 3-D float32 in/out");
+    if (!is_contiguous(in) || !is_contiguous(out)) MI_UNSUP(who, "needs C-contiguous arrays");
+    if (in->data == out->data) MI_UNSUP(who, "in-place");
     const int nd = in->ndim;
     const int64_t nz = nd == 3 ? in->shape[0] : 1, ny = in->shape[nd - 2], nx = in->shape[nd - 1];
-    if (nz < 1 || ny < 1 || nx < 8 || (nx & 3)) UNSUP("x extent must be a multiple of 4, >= 8");
-    { const int64_t tail = nx & 255; if (tail != 0 && tail < 8) UNSUP("x extent unsuitable for the streaming x window"); }
-    if (nz * ny * nx * 4 >= ((int64_t)1 << 31)) UNSUP("needs an array < 2 GiB");
-    if (((uintptr_t)in->data & 15) || ((uintptr_t)out->data & 15)) UNSUP("needs 16-byte aligned data");
-    if (nrows < 1 || nrows > 9 || !(nrows & 1)) UNSUP("1, 3, 5, 7 or 9 footprint rows");
+    if (nz < 1 || ny < 1 || nx < 8 || (nx & 3)) MI_UNSUP(who, "x extent must be a multiple of 4, >= 8");
+    { const int64_t tail = nx & 255; if (tail != 0 && tail < 8) MI_UNSUP(who, "x extent unsuitable for the streaming x window"); }
+    if (nz * ny * nx * 4 >= ((int64_t)1 << 31)) MI_UNSUP(who, "needs an array < 2 GiB");
+    if (((uintptr_t)in->data & 15) || ((uintptr_t)out->data & 15)) MI_UNSUP(who, "needs 16-byte aligned data");
+    if (nrows < 1 || nrows > 9 || !(nrows & 1)) MI_UNSUP(who, "1, 3, 5, 7 or 9 footprint rows");
     RunsF32Params p;
     memset(&p, 0, sizeof(p));
     bool any = false;
     for (int r = 0; r < 9; r++) p.hw[r] = -1;
     for (int r = 0; r < nrows; r++) {
-        if (half_width[r] < -1 || half_width[r] > 4) UNSUP("runs of at most 9 pixels");
+        if (half_width[r] < -1 || half_width[r] > 4) MI_UNSUP(who, "runs of at most 9 pixels");
         p.hw[r] = half_width[r];
         any = any || half_width[r] >= 0;
     }
-    if (!any) UNSUP("empty footprint");
+    if (!any) MI_UNSUP(who, "empty footprint");
     p.nx = (int)nx; p.ny = (int)ny; p.nz = (int)nz;
     p.my = filter_mode(mode[0]); p.mx = filter_mode(mode[1]);
     p.cval = (float)cval;
@@ -624,5 +601,4 @@ extern "C" int mi_minmax_runs_f32(const mi_array *in, const mi_array *out, int n
     case 7: return launch_runs_f32<7>(ip, op, p, is_max != 0, s);
     default: return launch_runs_f32<9>(ip, op, p, is_max != 0, s);
     }
-#undef UNSUP
 }

@@ -55,6 +55,44 @@ __device__ __forceinline__ int xcd_block(int b, int nblocks, int enabled)
     return (enabled && (nblocks & 7) == 0) ? (b & 7) * (nblocks >> 3) + (b >> 3) : b;
 }
 
+// Waves the chip holds at once: 256 CUs x 16 resident waves.  A streaming launch with more waves than this runs in rounds.
+constexpr int kStreamResidentWaves = 4096;
+
+// How a streaming launch cuts its streamed axis (n_axis samples) into chunks; every (line, chunk) pair is one wave.
+// Model: time ~ rounds x (chunk + ramp + 4), a round being kStreamResidentWaves waves and the ramp the samples a wave
+// reads before its first output (window - 1).  Volumes have many lines and get few long chunks, images (a handful of
+// columns) many short ones.  More chunks are taken only for a gain above 0.1 %; no chunk is shorter than min_chunk
+// (unless one chunk is), no more than max_chunks are tried.  Plain host arithmetic: mi_debug_plan_stream_chunks
+// (stream3d.hip) exposes it to the tests.
+static inline void plan_stream_chunks(int nlines, int n_axis, int ramp, int min_chunk, int max_chunks, int *chunk, int *nchunks)
+{
+    int nch = 1;
+    double best = 1e300;
+    for (int c = 1; c <= n_axis && c <= max_chunks; c++) {
+        const int ck = (n_axis + c - 1) / c;
+        if (c > 1 && ck < min_chunk) break;
+        const int real = (n_axis + ck - 1) / ck;
+        const double rounds = std::max(1.0, (double)nlines * real / (double)kStreamResidentWaves);
+        const double cost = rounds * (ck + ramp + 4.0);
+        if (cost < best * 0.999) { best = cost; nch = real; }
+    }
+    *chunk = (n_axis + nch - 1) / nch;
+    *nchunks = (n_axis + *chunk - 1) / *chunk;
+}
+
+// refusal of an entry point: the Python layer takes another route
+#define MI_UNSUP(who, msg) do { mi::set_error("%s: %s", who, msg); return MI_ERR_UNSUPPORTED; } while (0)
+
+// switch over odd tap counts 1..33 for one template slot
+#define MI_ODD_CASES(X) X(1) X(3) X(5) X(7) X(9) X(11) X(13) X(15) X(17) X(19) X(21) X(23) X(25) X(27) X(29) X(31) X(33)
+
+// the fill value of constant mode in the 8- and 16-bit kernels: is it a value of the dtype, and the dword of copies
+// the kernels take it as
+static inline bool cval_fits_u8(int cval) { return cval >= 0 && cval <= 255; }
+static inline unsigned pack_cval4(int cval) { return (unsigned)cval * 0x01010101u; }
+static inline bool cval_fits_16(int cval, bool is_signed) { return cval >= (is_signed ? -32768 : 0) && cval <= (is_signed ? 32767 : 65535); }
+static inline unsigned pack_cval2(int cval) { return ((unsigned)cval & 0xFFFFu) * 0x10001u; }
+
 // what a pass computes: weighted sum, or running minimum / maximum
 enum { SP_CORR = 0, SP_MIN = 1, SP_MAX = 2 };
 

@@ -268,20 +268,7 @@ static int launch_stream_d(const double *in, double *out, StreamParamsD &p, hipS
     const int nA = p.axis == 0 ? p.nz : p.ny;
     const int nother = p.axis == 0 ? p.ny : p.nz;
     const int nlines = nother * p.nxt;
-    int nch = 1;
-    {
-        double best = 1e300;
-        for (int c = 1; c <= nA && c <= 1024; c++) {
-            const int chunk = (nA + c - 1) / c;
-            if (c > 1 && chunk < 16) break;
-            const int real = (nA + chunk - 1) / chunk;
-            const double rounds = std::max(1.0, (double)nlines * real / 4096.0);
-            const double cost = rounds * (chunk + (WA - 1) + 4.0);
-            if (cost < best * 0.999) { best = cost; nch = real; }
-        }
-    }
-    p.chunk = (nA + nch - 1) / nch;
-    p.nchunks = (nA + p.chunk - 1) / p.chunk;
+    plan_stream_chunks(nlines, nA, WA - 1, 16, 1024, &p.chunk, &p.nchunks);
     const int waves = nlines * p.nchunks;
     p.swz = xcd_swizzle_for((size_t)p.nx * p.ny * p.nz * 8);
     note_kernel("mi::stream_pass_f64_kernel<%d,%d,%d,%d> grid=%d", WX, WA, DEPTH, (int)OP, (waves + 3) / 4);
@@ -289,8 +276,6 @@ static int launch_stream_d(const double *in, double *out, StreamParamsD &p, hipS
     MI_HIP(hipGetLastError());
     return MI_OK;
 }
-
-#define MI_ODD_CASES_D(X) X(1) X(3) X(5) X(7) X(9) X(11) X(13) X(15) X(17) X(19) X(21) X(23) X(25) X(27) X(29) X(31) X(33)
 
 // one streaming pass along `axis` with `wa` taps, x pass with `wx` taps fused (wx == wa <= 17, or one of them 1)
 static int run_stream_pass_f64(const double *in, double *out, int nz, int ny, int nx, int axis, const double *wav, int wa,
@@ -308,19 +293,19 @@ static int run_stream_pass_f64(const double *in, double *out, int nz, int ny, in
     if (wx == 1) {
         switch (wa) {
 #define X(N) case N: return launch_stream_d<1, N, SP_CORR>(in, out, p, s);
-            MI_ODD_CASES_D(X)
+            MI_ODD_CASES(X)
 #undef X
         }
     } else if (wa == 1) {
         switch (wx) {
 #define X(N) case N: if constexpr (N > 1) return launch_stream_d<N, 1, SP_CORR>(in, out, p, s); break;
-            MI_ODD_CASES_D(X)
+            MI_ODD_CASES(X)
 #undef X
         }
     } else if (wx == wa) {
         switch (wx) {
 #define X(N) case N: if constexpr (N <= 17 && N > 1) return launch_stream_d<N, N, SP_CORR>(in, out, p, s); break;
-            MI_ODD_CASES_D(X)
+            MI_ODD_CASES(X)
 #undef X
         }
     }
@@ -350,15 +335,13 @@ static int f64_geometry(const mi_array *in, const mi_array *out, const char *who
     int rc;
     if ((rc = check_array(in, "in")) || (rc = check_array(out, "out"))) return rc;
     MI_REQUIRE(same_shape(in, out), MI_ERR_INVALID_ARG, "output shape is not correct");
-#define UNSUP(msg) do { set_error("%s: %s", who, msg); return MI_ERR_UNSUPPORTED; } while (0)
-    if (in->ndim != 3 || in->dtype != MI_F64 || out->dtype != MI_F64) UNSUP("needs 3-D float64 in/out");
-    if (!is_contiguous(in) || !is_contiguous(out)) UNSUP("needs C-contiguous arrays");
-    if (in->data == out->data) UNSUP("in-place");
+    if (in->ndim != 3 || in->dtype != MI_F64 || out->dtype != MI_F64) MI_UNSUP(who, "needs 3-D float64 in/out");
+    if (!is_contiguous(in) || !is_contiguous(out)) MI_UNSUP(who, "needs C-contiguous arrays");
+    if (in->data == out->data) MI_UNSUP(who, "in-place");
     *nz = in->shape[0]; *ny = in->shape[1]; *nx = in->shape[2];
-    if (*nz < 1 || *ny < 1 || *nx < 4 || (*nx & 1)) UNSUP("x extent must be even, >= 4");
-    if (*nz * *ny * *nx * 8 >= ((int64_t)1 << 31)) UNSUP("needs an array < 2 GiB");
-    if (((uintptr_t)in->data & 15) || ((uintptr_t)out->data & 15)) UNSUP("needs 16-byte aligned data");
-#undef UNSUP
+    if (*nz < 1 || *ny < 1 || *nx < 4 || (*nx & 1)) MI_UNSUP(who, "x extent must be even, >= 4");
+    if (*nz * *ny * *nx * 8 >= ((int64_t)1 << 31)) MI_UNSUP(who, "needs an array < 2 GiB");
+    if (((uintptr_t)in->data & 15) || ((uintptr_t)out->data & 15)) MI_UNSUP(who, "needs 16-byte aligned data");
     return MI_OK;
 }
 
@@ -475,17 +458,16 @@ median3x3_f64_kernel(const double *__restrict__ in, double *__restrict__ out, co
 
 int run_median3x3_f64(const mi_array *in, const mi_array *out, int mx, int my, double cval, hipStream_t s)
 {
-#define UNSUP(msg) do { set_error("median3x3: %s", msg); return MI_ERR_UNSUPPORTED; } while (0)
-    if ((in->ndim != 2 && in->ndim != 3) || in->dtype != MI_F64 || out->dtype != MI_F64) UNSUP("needs 2-D / 3-D float64 in/out");
-    if (!is_contiguous(in) || !is_contiguous(out)) UNSUP("needs C-contiguous arrays");
-    if (in->data == out->data) UNSUP("in-place");
+    const char *const who = "median3x3";
+    if ((in->ndim != 2 && in->ndim != 3) || in->dtype != MI_F64 || out->dtype != MI_F64) MI_UNSUP(who, "needs 2-D / 3-D float64 in/out");
+    if (!is_contiguous(in) || !is_contiguous(out)) MI_UNSUP(who, "needs C-contiguous arrays");
+    if (in->data == out->data) MI_UNSUP(who, "in-place");
     const int nd = in->ndim;
     const int64_t nz = nd == 3 ? in->shape[0] : 1, ny = in->shape[nd - 2], nx = in->shape[nd - 1];
-    if (nz < 1 || ny < 1 || nx < 4 || (nx & 1)) UNSUP("x extent must be even, >= 4");
-    { const int64_t tail = nx & 127; if (tail != 0 && tail < 4) UNSUP("x extent unsuitable for the streaming x window"); }
-    if (nz * ny * nx * 8 >= ((int64_t)1 << 31)) UNSUP("needs an array < 2 GiB");
-    if (((uintptr_t)in->data & 15) || ((uintptr_t)out->data & 15)) UNSUP("needs 16-byte aligned data");
-#undef UNSUP
+    if (nz < 1 || ny < 1 || nx < 4 || (nx & 1)) MI_UNSUP(who, "x extent must be even, >= 4");
+    { const int64_t tail = nx & 127; if (tail != 0 && tail < 4) MI_UNSUP(who, "x extent unsuitable for the streaming x window"); }
+    if (nz * ny * nx * 8 >= ((int64_t)1 << 31)) MI_UNSUP(who, "needs an array < 2 GiB");
+    if (((uintptr_t)in->data & 15) || ((uintptr_t)out->data & 15)) MI_UNSUP(who, "needs 16-byte aligned data");
     Med2dParamsD p;
     memset(&p, 0, sizeof(p));
     p.nx = (int)nx; p.ny = (int)ny; p.nz = (int)nz;
@@ -493,7 +475,7 @@ int run_median3x3_f64(const mi_array *in, const mi_array *out, int mx, int my, d
     p.cval = cval;
     p.nxt = (int)((nx + 127) / 128);
     const int nlines = p.nz * p.nxt;
-    int nch = (4096 + nlines - 1) / nlines;
+    int nch = (kStreamResidentWaves + nlines - 1) / nlines;      // fill the chip once, chunks of at least 16 rows
     if (nch > p.ny / 16) nch = p.ny / 16;
     if (nch < 1) nch = 1;
     p.chunk = (p.ny + nch - 1) / nch;
@@ -518,16 +500,16 @@ extern "C" int mi_separable3d_f64(const mi_array *in, const mi_array *out, const
     int rc = f64_geometry(in, out, "separable3d_f64", &nz, &ny, &nx);
     if (rc) return rc;
     MI_REQUIRE(weights && wlen && origin && mode, MI_ERR_INVALID_ARG, "NULL argument");
-#define UNSUP(msg) do { set_error("separable3d_f64: %s", msg); return MI_ERR_UNSUPPORTED; } while (0)
+    const char *const who = "separable3d_f64";
     int w[3], off[3];
     for (int a = 0; a < 3; a++) {
         w[a] = weights[a] ? wlen[a] : 1;
-        if (w[a] < 1 || w[a] > kStreamMaxTaps || !(w[a] & 1)) UNSUP("taps must be odd and <= 33");
+        if (w[a] < 1 || w[a] > kStreamMaxTaps || !(w[a] & 1)) MI_UNSUP(who, "taps must be odd and <= 33");
         off[a] = w[a] / 2 + (weights[a] ? origin[a] : 0);
         if (off[a] < 0 || off[a] >= w[a]) { set_error("invalid origin"); return MI_ERR_INVALID_ARG; }
     }
-    if (weights[2] && origin[2] != 0) UNSUP("x origin must be 0");
-    if (!x_extent_ok(nx, w[2])) UNSUP("x extent unsuitable for the streaming x pass");
+    if (weights[2] && origin[2] != 0) MI_UNSUP(who, "x origin must be 0");
+    if (!x_extent_ok(nx, w[2])) MI_UNSUP(who, "x extent unsuitable for the streaming x pass");
     const int mz = filter_mode(mode[0]), my = filter_mode(mode[1]), mx = filter_mode(mode[2]);
     if (mz == MI_MODE_CONSTANT || my == MI_MODE_CONSTANT || mx == MI_MODE_CONSTANT) {
         // SciPy extends the INTERMEDIATE array of every pass by cval; the passes here run in another order (x first),
@@ -536,7 +518,7 @@ extern "C" int mi_separable3d_f64(const mi_array *in, const mi_array *out, const
             if (!weights[a]) continue;
             double sum = 0.0;
             for (int k = 0; k < w[a]; k++) sum += weights[a][k];
-            if (fabs(sum - 1.0) > 4e-16 * w[a]) UNSUP("constant mode needs kernels that sum to one");
+            if (fabs(sum - 1.0) > 4e-16 * w[a]) MI_UNSUP(who, "constant mode needs kernels that sum to one");
         }
     }
     hipStream_t s = resolve_stream(stream);
@@ -548,7 +530,7 @@ extern "C" int mi_separable3d_f64(const mi_array *in, const mi_array *out, const
     if (w[2] > 1 && !fuse_xz && !fuse_xy) passes[np++] = {1, 1, 0, my, w[2]};      // x only (streams over y)
     if (w[0] > 1) passes[np++] = {0, w[0], off[0], mz, fuse_xz ? w[2] : 1};
     if (w[1] > 1) passes[np++] = {1, w[1], off[1], my, fuse_xy ? w[2] : 1};
-    if (np == 0) UNSUP("nothing to filter");
+    if (np == 0) MI_UNSUP(who, "nothing to filter");
     const size_t bytes = (size_t)(nz * ny * nx) * sizeof(double);
     void *tmp[2] = {nullptr, nullptr};
     for (int t = 0; t < np - 1 && t < 2; t++)
@@ -563,7 +545,6 @@ extern "C" int mi_separable3d_f64(const mi_array *in, const mi_array *out, const
     }
     for (int t = 0; t < 2; t++) if (tmp[t]) pool_free(tmp[t]);
     return rc;
-#undef UNSUP
 }
 
 /* Separable flat min / max on a float64 volume / image, odd sizes <= 9 (declared in include/mi355img.h). */
@@ -574,16 +555,16 @@ extern "C" int mi_minmax3d_f64(const mi_array *in, const mi_array *out, const in
     int rc = f64_geometry(in, out, "minmax3d_f64", &nz, &ny, &nx);
     if (rc) return rc;
     MI_REQUIRE(size && origin && mode, MI_ERR_INVALID_ARG, "NULL argument");
-#define UNSUP(msg) do { set_error("minmax3d_f64: %s", msg); return MI_ERR_UNSUPPORTED; } while (0)
+    const char *const who = "minmax3d_f64";
     int w[3], off[3];
     for (int a = 0; a < 3; a++) {
         w[a] = size[a];
-        if (w[a] < 1 || w[a] > 9 || !(w[a] & 1)) UNSUP("sizes must be odd and <= 9");
+        if (w[a] < 1 || w[a] > 9 || !(w[a] & 1)) MI_UNSUP(who, "sizes must be odd and <= 9");
         off[a] = w[a] / 2 + origin[a];
         if (off[a] < 0 || off[a] >= w[a]) { set_error("invalid origin"); return MI_ERR_INVALID_ARG; }
     }
-    if (origin[2] != 0) UNSUP("x origin must be 0");
-    if (!x_extent_ok(nx, w[2])) UNSUP("x extent unsuitable for the streaming x pass");
+    if (origin[2] != 0) MI_UNSUP(who, "x origin must be 0");
+    if (!x_extent_ok(nx, w[2])) MI_UNSUP(who, "x extent unsuitable for the streaming x pass");
     const int mz = filter_mode(mode[0]), my = filter_mode(mode[1]), mx = filter_mode(mode[2]);
     hipStream_t s = resolve_stream(stream);
     struct Pass { int axis, wa, oa, ma, wx; };
@@ -594,7 +575,7 @@ extern "C" int mi_minmax3d_f64(const mi_array *in, const mi_array *out, const in
     if (w[2] > 1 && !fuse_xz && !fuse_xy) passes[np++] = {1, 1, 0, my, w[2]};
     if (w[0] > 1) passes[np++] = {0, w[0], off[0], mz, fuse_xz ? w[2] : 1};
     if (w[1] > 1) passes[np++] = {1, w[1], off[1], my, fuse_xy ? w[2] : 1};
-    if (np == 0) UNSUP("nothing to filter");
+    if (np == 0) MI_UNSUP(who, "nothing to filter");
     const size_t bytes = (size_t)(nz * ny * nx) * sizeof(double);
     void *tmp[2] = {nullptr, nullptr};
     for (int t = 0; t < np - 1 && t < 2; t++)
@@ -614,5 +595,4 @@ extern "C" int mi_minmax3d_f64(const mi_array *in, const mi_array *out, const in
     }
     for (int t = 0; t < 2; t++) if (tmp[t]) pool_free(tmp[t]);
     return rc;
-#undef UNSUP
 }

@@ -27,6 +27,8 @@ int mi_debug_set_long_rows(int k);            /* long kernel: 0 auto (r3 kernel)
 int mi_debug_set_minmax_f32_fused(int on);
 int mi_debug_stream_pass(const float *in, float *out, int nz, int ny, int nx, int axis, const float *wav, int wa,
                          int oa, int ma, const float *wxv, int wx, int mx, float cval, mi_stream stream);
+/* the chunk plan of a streaming launch (csrc/stream3d.hpp plan_stream_chunks): host arithmetic, no device needed */
+int mi_debug_plan_stream_chunks(int nlines, int n_axis, int ramp, int min_chunk, int max_chunks, int *chunk, int *nchunks);
 /* plain float4 copy kernel (grid-stride, `blocks` workgroups of 256): the practical HBM ceiling for a byte count */
 int mi_debug_copy_f32(const float *in, float *out, int64_t n, int blocks, mi_stream stream);
 int mi_debug_copy_f32_nt(const float *in, float *out, int64_t n, int blocks, mi_stream stream);   /* r4: 4 loads in flight, non-temporal loads and stores */
